@@ -17,8 +17,17 @@ SURVEY §8(e) c5) -- weak scaling, no data-path collective; torch.distributed
 Each rank is one independent encoder, as the reference's one hl_codec_t per
 stream (hl_codec.c:22-61).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(the headline figure, ms_per_step, how the timed call ran).  --dump-outputs
+DIR then also writes what the timed call returned for its last step
+(dump_outputs below).  --full adds everything else, after the timed region:
+the bit-exactness check of every encoded frame against the reference
+encoder's MD5s, the roofline figures (k_pipeline with the recorded counters
+and its critical path, a run of k_planes on its own) and the CPU baseline
+(--no-cpu-baseline leaves that one out).
 
 Without torchrun (WORLD_SIZE unset) and N > 1, this process only launches N
 rank processes (one per GPU, LOCAL_RANK = device) and returns their exit
@@ -234,6 +243,67 @@ def svc_cpu_baseline(clips, g, n_aus, first, steps):
     }
 
 
+def bench_clip(n_frames, seed):
+    """The first n_frames of the BENCH_CLIP_FRAMES-frame synthetic stream of
+    this seed (synth.clip(W, H, BENCH_CLIP_FRAMES, seed)[:n_frames]) without
+    generating the frames after them: a frame depends on the clip length and
+    on the frames before it only."""
+    import itertools
+
+    import numpy as np
+
+    from hartallo_amd import synth
+
+    it = itertools.islice(synth.frames(W, H, max(n_frames, BENCH_CLIP_FRAMES), seed), n_frames)
+    return np.stack([np.concatenate([y.ravel(), u.ravel(), v.ravel()]) for y, u, v in it])
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def npy_saver(path, limit):
+    """save(name, array) writes path/<name>.npy while the files written so
+    far stay within `limit` bytes; an array that would pass it is left out."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    left = [limit]
+
+    def save(name, a):
+        if a.nbytes + 128 <= left[0]:  # 128: the .npy header
+            left[0] -= a.nbytes + 128
+            np.save(os.path.join(path, name + ".npy"), a)
+    return save
+
+
+def dump_outputs(path, rank, encs):
+    """--dump-outputs: what the timed call handed back for its last step (the
+    last timed frame), per stream, as float32 / float64 .npy files:
+      bitstream     the frame's Annex-B bytes (headers when signalled, start
+                    code, slice NAL), one value per byte
+      frame_bytes   slice NAL bytes of every timed frame (float64)
+      recon         the frame's reconstructed picture, planar Y|U|V
+                    (hl_amd_get_recon: the picture the next frame would
+                    predict from, so it carries the whole chain of timed P
+                    pictures before it)
+    Stream s > 0 of a process adds _s<s> to the name and rank r > 0 adds
+    _r<r>.  The recon is left out for the streams that would take the
+    directory past DUMP_LIMIT_BYTES."""
+    import numpy as np
+
+    put = npy_saver(path, DUMP_LIMIT_BYTES // max(1, int(os.environ.get("WORLD_SIZE", "1"))))  # every rank its share
+
+    def save(name, si, a):
+        put(name + (f"_s{si}" if si else "") + (f"_r{rank}" if rank else ""), a)
+
+    for si, e in enumerate(encs):
+        rs = e.last_batch_results()
+        save("bitstream", si, np.frombuffer(rs[-1].annexb(), np.uint8).astype(np.float32))
+        save("frame_bytes", si, np.array([len(r.data) for r in rs], np.float64))
+    for si, e in enumerate(encs):
+        save("recon", si, np.concatenate(e.recon()).astype(np.float32))
+
+
 def check_bitexact(outputs, seed):
     """True / False when every frame's Annex-B output matches the reference
     encoder's MD5 for this stream (tests/golden/bench_golden.json), None when
@@ -383,13 +453,20 @@ def run_svc(args):
     else:
         groups = sorted({svc_pipeline.role_of(r, world, L).group for r in range(world)})
         member_of = {gi: [r for r in range(world) if svc_pipeline.role_of(r, world, L).group == gi] for gi in groups}
-    ok = True
+    ok = None
+    put = npy_saver(args.dump_outputs, DUMP_LIMIT_BYTES) if args.dump_outputs and rank == 0 else None
     for gi in groups:
         members = member_of[gi]
         aus = svc_pipeline.assemble([allp[r] for r in members])
-        ok = ok and [hashlib.md5(a).hexdigest() for a in aus] == g["au_md5"][:n]
+        if put:  # the last timed access unit of every stream (one value per byte) and every timed access unit's size
+            import numpy as np
+
+            put("access_unit" + (f"_g{gi}" if gi else ""), np.frombuffer(aus[-1], np.uint8).astype(np.float32))
+            put("access_unit_bytes" + (f"_g{gi}" if gi else ""), np.array([len(a) for a in aus[args.warmup:]], np.float64))
+        if args.full:
+            ok = ok is not False and [hashlib.md5(a).hexdigest() for a in aus] == g["au_md5"][:n]
     roofline = base = None
-    if rank == 0 and streams:
+    if rank == 0 and streams and args.full:
         # dominant kernel: k_pipeline of the base run (one launch per batch);
         # algorithmic bytes = 2752 B per base MB x MBs per launch
         ms = enc.timing_ms()
@@ -414,6 +491,7 @@ def run_svc(args):
                        "parallelism": ("all layers on one GPU per stream, base layer frame-pipelined, enhancement layers "
                                        "overlapping the base run") if streams else "layer-sharded",
                        "exchange": ("rccl" if nccl else "gloo-host") if not streams else None},
+            "full": args.full,  # without --full: no check against the reference (bitexact null), no roofline, no CPU baseline
             "bitexact": ok,
             "bitexact_check": "every access unit (warm-up and timed) of every stream vs the reference encoder's per-AU MD5s "
                               "(tests/golden/svc_golden.json, oracle/_ref/ref_svc)",
@@ -543,6 +621,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--streams", type=int, default=1, help="streams per process, in shared pipelined runs (hl_amd_encode_streams)")
     ap.add_argument("--svc", action="store_true", help="BASELINE config 4 (spatial SVC) instead of the headline workload")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the bit-exactness check against the reference encoder's MD5s, "
+                         "the roofline figures (k_pipeline, recorded counters, the k_planes run) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call returned for its last step as DIR/<name>.npy")
     args = ap.parse_args()
     world_req, launch = resolve_world(args.gpus)
     if launch:  # before anything imports torch or touches a GPU
@@ -556,7 +639,7 @@ def main():
 
     import torch
 
-    from hartallo_amd import Encoder, dist, synth
+    from hartallo_amd import Encoder, dist
 
     rank, world, local = dist.init_from_env()
     if world != world_req:
@@ -569,7 +652,7 @@ def main():
     n_frames = args.warmup + args.steps
     K = max(1, args.streams)  # streams this process encodes (one encoder each, shared pipelined runs)
     seeds = [dist.stream_seed(rank * K + si) for si in range(K)]
-    frames_host = [synth.clip(W, H, max(n_frames, BENCH_CLIP_FRAMES), sd)[:n_frames] for sd in seeds]
+    frames_host = [bench_clip(n_frames, sd) for sd in seeds]
     # inputs resident in HBM before timing
     devs = [torch.from_numpy(fh).to(f"cuda:{local}") for fh in frames_host]
     torch.cuda.synchronize()
@@ -610,8 +693,9 @@ def main():
     outputs = [[] for _ in range(K)]
     warm = {k: 0 for k in STAT_KEYS}
     if args.warmup:  # same entry point as the timed frames (warms the pipelined path and its buffers)
-        for si, rs in enumerate(encode(0, args.warmup, True)):
-            outputs[si] += [r.annexb() for r in rs]
+        for si, rs in enumerate(encode(0, args.warmup, args.full)):
+            if args.full:  # kept for the bit-exactness check
+                outputs[si] += [r.annexb() for r in rs]
         warm = stats_sum()
     enc.set_timing(True)
     dist.barrier()
@@ -630,6 +714,46 @@ def main():
     pipeline["warmup_off_pipeline"] = tot[-1]
     pipeline["scope"] = ("timed call (hl_amd_last_batch_stats), summed over ranks (runs: launches); warmup_off_pipeline = "
                          "warm-up pictures not coded by a clean run")
+    if args.dump_outputs:  # before anything else runs on the encoders
+        dump_outputs(args.dump_outputs, rank, encs)
+
+    total = world * K * args.steps
+    fps = total / elapsed
+    line = {
+        "metric": "1080p encoded frames/sec (bit-exact) at 1/2/4/8 MI355X; macroblocks/sec/GPU",
+        "value": round(fps, 4),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8/int32",
+        "data": "synthetic (hartallo_amd.synth, seeded per rank)",
+        "config": {"workload": "1920x1088 YUV420 IPPP GOP30 QP28 ME16 deblock, one stream per GPU, frame-pipelined", "width": W, "height": H,
+                   "qp": QP, "me_range": ME_RANGE, "deblock": DEBLOCK, "gop": GOP, "parallelism": f"streams{world * K}",
+                   "streams_per_gpu": share * K, "streams_per_process": K},
+        "mb_per_s_per_gpu": round(fps / world * share * (W // 16) * (H // 16), 1),
+        # which physical GPUs ran: the process group's size and every rank's device
+        "process_group_world_size": pg_world,
+        "ranks": ranks,
+        "distinct_gpus": len({r["pci_bus_id"] for r in ranks}),
+        "warning": warning,
+        "bitexact": None,  # checked with --full only (null: not checked)
+        "pipeline": pipeline,
+        "bitstream_bytes_per_frame": round(out_bytes / args.steps, 1),
+        "full": args.full,
+    }
+    if not args.full:  # the headline figure only; --full adds the checks and the figures that take runs of their own
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        for e in encs:
+            e.close()
+        dist.shutdown()
+        return
+
     # bit-exactness of everything this rank encoded, outside the timed region
     bitexact = True
     for si, e in enumerate(encs):
@@ -653,8 +777,6 @@ def main():
         base = cpu_baseline(frames_host[0], min(args.cpu_frames, n_frames), args.warmup, args.steps)
 
     if rank == 0:
-        total = world * K * args.steps
-        fps = total / elapsed
         nmb = (W // 16) * (H // 16)
         # dominant kernel: k_pipeline (one launch per run of pictures);
         # algorithmic bytes per launch = 2752 B x MBs per launch
@@ -671,33 +793,10 @@ def main():
         cus = torch.cuda.get_device_properties(local).multi_processor_count
         valu_util = (round(pmc["valu_insts_per_mb"] * nmb * run_frames * K / avg_launch_s / (4 * cus * SHADER_CLOCK_HZ), 4)
                      if pmc and mb_launches == 1 else None)
-        line = {
-            "metric": "1080p encoded frames/sec (bit-exact) at 1/2/4/8 MI355X; macroblocks/sec/GPU",
-            "value": round(fps, 4),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed * 1e3 / args.steps, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8/int32",
-            "data": "synthetic (hartallo_amd.synth, seeded per rank)",
-            "config": {"workload": "1920x1088 YUV420 IPPP GOP30 QP28 ME16 deblock, one stream per GPU, frame-pipelined", "width": W, "height": H,
-                       "qp": QP, "me_range": ME_RANGE, "deblock": DEBLOCK, "gop": GOP, "parallelism": f"streams{world * K}",
-                       "streams_per_gpu": share * K, "streams_per_process": K},
-            "mb_per_s_per_gpu": round(fps / world * share * nmb, 1),
-            # which physical GPUs ran: the process group's size and every rank's device
-            "process_group_world_size": pg_world,
-            "ranks": ranks,
-            "distinct_gpus": len({r["pci_bus_id"] for r in ranks}),
-            "warning": warning,
+        line.update({
             "bitexact": bitexact_all if bitexact_all is None else bool(bitexact_all),
             "bitexact_check": "every frame of every rank (warm-up and timed) vs the reference encoder's per-frame MD5s "
                               "(tests/golden/bench_golden.json, oracle/_ref/ref_enc on the same synthetic stream)",
-            "pipeline": pipeline,
-            "bitstream_bytes_per_frame": round(out_bytes / args.steps, 1),
             "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,
                          "traffic": round(pmc["traffic_bytes_per_mb"] * nmb * run_frames * K) if pmc and mb_launches == 1 else None,
@@ -718,7 +817,7 @@ def main():
                                 "bytes_per_launch": planes_bytes, "avg_launch_us": round(planes_ms * 1e3, 2),
                                 "note": "50 back-to-back launches on the reference picture, HIP events on the encoder's stream"},
             "cpu_baseline": base,
-        }
+        })
         print(json.dumps(line), flush=True)
     for e in encs:
         e.close()

@@ -101,6 +101,39 @@ def test_spawn_ranks_deadline(tmp_path, monkeypatch):
     assert time.monotonic() - t < 60
 
 
+def test_bench_clip_is_the_head_of_the_whole_clip(monkeypatch):
+    """bench.bench_clip generates only the frames a run encodes; they are the
+    first frames of the BENCH_CLIP_FRAMES-frame stream the reference MD5s
+    (tests/golden/bench_golden.json) were made from, also when a run asks for
+    more frames than that."""
+    import numpy as np
+
+    from hartallo_amd import synth
+
+    monkeypatch.setattr(bench, "W", 48)
+    monkeypatch.setattr(bench, "H", 32)
+    monkeypatch.setattr(bench, "BENCH_CLIP_FRAMES", 7)
+    whole = synth.clip(48, 32, 7, 11)
+    for n in (1, 4, 7):
+        got = bench.bench_clip(n, 11)
+        assert got.dtype == np.uint8 and np.array_equal(got, whole[:n])
+    assert np.array_equal(bench.bench_clip(9, 12), synth.clip(48, 32, 9, 12))
+
+
+def test_dump_size_limit(tmp_path):
+    """--dump-outputs: an array that would take the directory past the limit
+    is left out, smaller ones after it are still written."""
+    import numpy as np
+
+    put = bench.npy_saver(str(tmp_path / "d"), 1000)
+    put("a", np.zeros(100, np.float32))   # 400 + 128 bytes
+    put("b", np.zeros(100, np.float32))   # would pass 1000
+    put("c", np.zeros(10, np.float64))
+    files = sorted(os.listdir(tmp_path / "d"))
+    assert files == ["a.npy", "c.npy"]
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in files) <= 1000
+
+
 def test_pmc_record_identity(tmp_path, monkeypatch):
     """bench.load_pmc: the counters are used on the library they were taken
     on, or on a relink of the same code (only the ELF string tables differ);

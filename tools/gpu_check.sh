@@ -7,8 +7,7 @@ timeout -k 10 400 python -u -m pytest -x -v --timeout 200 --timeout-method threa
 rc=$?
 tail -8 gpurun_out/parity.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python -u bench.py --steps 6 --warmup 1 --no-cpu-baseline > gpurun_out/bench.log 2>&1 || exit $?
-grep -v amdgpu.ids gpurun_out/bench.log
+bash tools/gpu_steps.sh check bench_short || exit $?  # bench.py --steps 6 --warmup 1 --full --no-cpu-baseline
 if [ "$1" = "profile" ]; then
   timeout -k 10 200 python -u tools/phase_profile.py 3 > gpurun_out/phase.log 2>&1 || exit $?
   grep -v amdgpu.ids gpurun_out/phase.log | tail -14

@@ -17,8 +17,6 @@ bash tools/gpu_round.sh $tag || exit 1
 echo "== per-frame API"
 timeout -k 10 200 python -u tools/per_frame_api.py 8 > gpurun_out/${tag}_per_frame_api.log 2>&1 || { tail -5 gpurun_out/${tag}_per_frame_api.log; exit 1; }
 grep '^{' gpurun_out/${tag}_per_frame_api.log
-echo "== svc"
-timeout -k 10 300 python -u bench.py --svc > gpurun_out/${tag}_svc_bench.log 2>&1 || { tail -5 gpurun_out/${tag}_svc_bench.log; exit 1; }
-grep '^{' gpurun_out/${tag}_svc_bench.log | cut -c1-300
+bash tools/gpu_steps.sh $tag svc_cpu || exit 1  # bench.py --svc --full, CPU baseline included
 echo "== share"
 NS="1 2" bash tools/gpu_share.sh

@@ -21,6 +21,6 @@ step() {  # name, seconds, command...
 }
 step tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
 step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"
-step bench_driver 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline
-step bench 400 python -u bench.py
+step bench_driver 300 python -u bench.py --steps 20 --warmup 5 --full --no-cpu-baseline
+step bench 400 python -u bench.py --full
 step prof 400 rocprofv3 --kernel-trace --stats -d "gpurun_out/${tag}_prof" -o run --output-format csv -- python3 bench.py --no-cpu-baseline

@@ -7,6 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 [ -n "$NOTEST" ] || bash tools/gpu_svc.sh || exit 1
 for cfg in ${CFGS:-8:0 31:0}; do
     c=${cfg%%:*}; w=${cfg##*:}
-    HL_AMD_SVC_CHUNK=$c HL_AMD_PIPE_WG=$w timeout -k 10 300 python -u bench.py --svc > gpurun_out/${tag}_c${c}_w${w}.log 2>&1 || { tail -20 gpurun_out/${tag}_c${c}_w${w}.log; exit 1; }
-    echo "chunk $c wg $w: $(grep -o '"value": [0-9.]*' gpurun_out/${tag}_c${c}_w${w}.log | head -1) $(grep -o '"bitexact": [a-z]*' gpurun_out/${tag}_c${c}_w${w}.log)"
+    # bench.py --svc --full (the bit-exactness check and the CPU baseline), logged by gpu_steps.sh as <tag>_c<c>_w<w>_svc_cpu.log
+    o=$(HL_AMD_SVC_CHUNK=$c HL_AMD_PIPE_WG=$w bash tools/gpu_steps.sh ${tag}_c${c}_w${w} svc_cpu) || { echo "$o"; exit 1; }
+    echo "chunk $c wg $w: $(echo "$o" | grep -o '"value": [0-9.]*' | head -1) $(echo "$o" | grep -o '"bitexact": [a-z]*')"
 done
