@@ -27,8 +27,10 @@ unit: tests/gpu_unit/libhl_unit.so
 hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -shared -o $@ $(KSRC) $(HOSTSRC)
 
-tests/emu/libhl_emu.so: tests/emu/hl_emu.hip $(HOSTSRC) $(HDRS)
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -O2 -DHL_FAM3=1 -shared -o $@ tests/emu/hl_emu.hip $(HOSTSRC)
+# (hl_emu_memo.hip = hl_emu.hip plus the memo's settings, counters and key export)
+EMUSRC := tests/emu/hl_emu_memo.hip
+tests/emu/libhl_emu.so: $(EMUSRC) tests/emu/hl_emu.hip $(HOSTSRC) $(HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -O2 -DHL_FAM3=1 -shared -o $@ $(EMUSRC) $(HOSTSRC)
 
 tests/gpu_unit/libhl_unit.so: tests/gpu_unit/hl_unit.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared -o $@ tests/gpu_unit/hl_unit.hip
@@ -49,7 +51,7 @@ tests/sanitize/hl_writer_asan.o: $(CSRC)/hl_writer.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) $(ASAN) $(UBSAN) -c -o $@ $<
 tests/sanitize/hl_rc_asan.o: $(CSRC)/hl_rc.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) $(ASAN) $(UBSAN) -c -o $@ $<
-tests/sanitize/hl_emu_asan.o: tests/emu/hl_emu.hip $(HDRS)
+tests/sanitize/hl_emu_asan.o: $(EMUSRC) tests/emu/hl_emu.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) -DHL_FAM3=1 $(ASAN) -c -o $@ $<
 tests/sanitize/libhl_emu_asan.so: tests/sanitize/hl_emu_asan.o tests/sanitize/hl_writer_asan.o tests/sanitize/hl_rc_asan.o
 	$(HIPCC) --offload-arch=$(ARCH) $(ASAN) $(UBSAN) -shared-libsan -shared -o $@ $^
@@ -59,8 +61,8 @@ tests/sanitize/rowgate_tsan: tests/sanitize/rowgate_tsan.cpp $(CSRC)/hl_writer.c
 # the kernel logic, run once per change of the shift / overflow idioms
 # (DESIGN.md §2); tests/test_sanitizers.py uses it when it is present
 ubsan: tests/sanitize/libhl_emu_ubsan.so
-tests/sanitize/libhl_emu_ubsan.so: tests/emu/hl_emu.hip $(HOSTSRC) $(HDRS)
-	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) -DHL_FAM3=1 $(ASAN) $(UBSAN) -shared-libsan -shared -o $@ tests/emu/hl_emu.hip $(HOSTSRC)
+tests/sanitize/libhl_emu_ubsan.so: $(EMUSRC) tests/emu/hl_emu.hip $(HOSTSRC) $(HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) -DHL_FAM3=1 $(ASAN) $(UBSAN) -shared-libsan -shared -o $@ $(EMUSRC) $(HOSTSRC)
 
 # profiling build: same library (same device scheduling flags) with per-phase
 # clock64 counters (tools/phase_profile.py)

@@ -958,6 +958,7 @@ struct hl_amd_encoder_s {
     bool helpers = true;                         // P macroblocks of pipelined runs get intra helper tasks
     int32_t helper_kept = 0, helper_rejected = 0, helper_self = 0;  // hl_amd_last_helper_stats
     int fam3 = 1;                                // ... and 8x8-family helper tasks (HL_AMD_FAM3: 0 off, 2 runs too)
+    int memo = kMemoSlots;                       // FrameArgs::memo: slots of the candidate evaluation's memo (HL_AMD_MEMO: 0 off, N slots)
     int32_t fam3_kept = 0, fam3_rejected = 0;    // hl_amd_last_fam3_stats
     Fam3Out* d_f3 = nullptr;                     // 8x8-family partitioning helper results [MB][4] ([slot][MB][4] with HL_AMD_FAM3=2)
     PipeFrame *d_pf, *h_pf;
@@ -1118,6 +1119,13 @@ extern "C" int32_t hl_amd_encoder_create(const hl_amd_params_t* p, hl_amd_encode
         e->helpers = !(h && atoi(h) == 0);
         const char* h3 = getenv("HL_AMD_FAM3");  // A/B knob
         e->fam3 = h3 ? atoi(h3) : 1;  // 0 off, 1 lone pictures, 2 runs of one stream too (their first / last pictures, HL_AMD_F3_EDGE)
+        const char* hm = getenv("HL_AMD_MEMO");  // A/B knob: unset = the built capacity, 0 = off, N = N slots (a power of two)
+        e->memo = hm ? atoi(hm) : kMemoSlots;
+        if (e->memo < 0 || e->memo > kMemoSlots || (e->memo & (e->memo - 1))) {
+            free_all(e);
+            delete e;
+            return HL_AMD_ERROR_INVALID_PARAMETER;
+        }
     }
     e->reach = 2;
     e->window = 64;
@@ -1212,6 +1220,7 @@ static int32_t encode_frame(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t
     F.is_intra = intra;
     F.me_range = std::min(64, std::max(1, e->p.me_range));
     F.early_term = e->p.me_early_term != 0;
+    F.memo = e->memo;
     F.lambda = rdo_lambda(qp);  // slice.c:1766
     F.src[0] = y;
     F.src[1] = u;
@@ -1448,6 +1457,7 @@ static FrameArgs frame_args(hl_amd_encoder_t* e, bool intra, int qp)
     F.is_intra = intra;
     F.me_range = std::min(64, std::max(1, e->p.me_range));
     F.early_term = e->p.me_early_term != 0;
+    F.memo = e->memo;
     F.lambda = rdo_lambda(qp);  // slice.c:1766
     F.pstride = e->pstride;
     F.plsz = (int32_t)e->plsz;

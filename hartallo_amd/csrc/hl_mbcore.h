@@ -125,12 +125,58 @@ constexpr int kQPass = kMbThreads >= 512 ? HL_QPASS : (9 * 16 + (kMbThreads >> 2
 constexpr int kPassItems = kQPass * (kMbThreads >> 2);
 constexpr int kSpecMaxBlocks = HL_SPEC_MAX_BLOCKS;
 
+// Memo of the per-block candidate evaluation (Shared::memo, eval_candidates
+// phase 1): what phase 1 computes for one 4x4 block of one
+// candidate depends on the block's position in the MB, the prediction samples
+// it reads and the picture's QP only, and the partition searches of one MB
+// evaluate the same (prediction, block) pairs again and again.
+//
+// Key (32 bits, never 0; 0 = empty slot):
+//   bits  0..10  dx: the partition's clamped integer displacement in x
+//                (put_cand's clip3 applied, minus the unclamped origin), two's complement
+//   bits 11..21  dy likewise
+//   bits 22..25  quarter-pel phase (mvy & 3) << 2 | (mvx & 3)
+//   bit  26      1 (a key is never zero)
+//   bits 27..30  the block's raster index in the MB, (by >> 2) * 4 + (bx >> 2)
+//   bit  31      kMemoPending: claimed, not yet visible to probes
+// The block's prediction origin is (xL + bx + dx, yL + by + dy): the clamp
+// moves the partition's origin, and every block of the partition with it.
+// So EQUAL KEYS => IDENTICAL o1, o2 ROWS AND IDENTICAL SOURCE ROW of every
+// lane of the quad, whatever partition and MV the candidate came from.  A
+// displacement outside [-1024, 1023] does not fit: that candidate bypasses the
+// table (no probe, no insert) and is computed.
+#ifndef HL_MEMO_SLOTS
+#define HL_MEMO_SLOTS 1024  // built capacity (a power of two); FrameArgs::memo picks the slots in use
+#endif
+constexpr int kMemoSlots = HL_MEMO_SLOTS;
+constexpr int kMemoProbe = 4;  // linear probe length: lane r of a quad looks at slot hash + r
+constexpr uint32_t kMemoPending = 1u << 31;
+static_assert(kMemoSlots >= kMemoProbe && (kMemoSlots & (kMemoSlots - 1)) == 0, "memo slots: a power of two");
+// the candidate's part of the key (put_cand keeps it in CandSlot::pad >> 4); 0 = does not fit
+__host__ __device__ inline uint32_t memo_kbase(int dx, int dy, int ph)
+{
+    const bool fit = ((uint32_t)(dx + 1024) | (uint32_t)(dy + 1024)) < 2048u;  // both in [-1024, 1023]
+    return fit ? (1u << 26) | ((uint32_t)ph << 22) | (((uint32_t)dy & 0x7FFu) << 11) | ((uint32_t)dx & 0x7FFu) : 0u;
+}
+__host__ __device__ inline uint32_t memo_key(uint32_t kbase, int blk) { return kbase | ((uint32_t)blk << 27); }
+// first slot of a key's probe window among 1 << lg slots
+__host__ __device__ inline int memo_hash(uint32_t key, int lg) { return lg ? (int)((key * 0x9E3779B1u) >> (32 - lg)) : 0; }
+#if defined(HL_EMU_BUILD) && !defined(__HIP_DEVICE_COMPILE__)
+// the emulator's memo settings and counters (tests/emu/hl_emu_memo.hip, emu_set_memo / emu_memo_stats)
+extern int g_emu_memo_slots;  // slots in use on the host path (the device's: FrameArgs::memo)
+extern int g_emu_memo_probe;  // probe length of the host path (the device's is kMemoProbe)
+enum { MS_ITEMS, MS_HITS, MS_BYPASSED, MS_NOT_INSERTED, MS_INSERTED, MS_MB_KEYS_MAX, MS_MBS, MS_PASSES, MS_PASSES_ALL_HIT,
+       MS_ROUNDS, MS_ROUNDS_MISS, MS_WAVE_ROUNDS, MS_WAVE_ROUNDS_MISS, MS_COUNT };
+extern long long g_emu_memo_stat[MS_COUNT];
+extern int g_emu_memo_mb;     // keys the current MB (a helper task counts as one) inserted or could not insert; -1 before its first evaluation
+#endif
+
 // One candidate of a step: plane offsets of its quarter-pel prediction
 // (second plane = first when the phase needs no average) and its MV.
 struct alignas(16) CandSlot {
     int32_t off1, off2;
     int16_t mvx, mvy;
-    int32_t pad;
+    int32_t pad;  // diamond point index | memo_kbase << 4
 };
 constexpr int kNA = -1;   // not-available sample marker
 
@@ -199,6 +245,7 @@ struct FrameArgs {
     int32_t W, H, Wc, Hc, mbw, mbh;
     int32_t qp, qpc, is_intra, me_range;
     int32_t early_term;     // hl_codec_t.me_early_term_flag (rdo.c:888-931)
+    int32_t memo;           // slots of Shared::memo in use (a power of two <= kMemoSlots; 0 = no memo)
     double lambda;
     const uint8_t* src[3];
     uint8_t* cur[3];
@@ -272,8 +319,10 @@ struct Shared {
     int32_t cbp_l, cbp_c; // live CodedBlockPattern{Luma,Chroma}
     // --- candidate step scratch
     CandSlot wc[kMaxWaves][kMaxCand];  // candidates of the step, one copy per wave (each wave writes its own)
+#if !defined(__HIP_DEVICE_COMPILE__)  // (host path only: the device image spends their 12 KB on the memo)
     int32_t be_nz[kMaxCand][16], be_tc[kMaxCand][16], be_t1[kMaxCand][16], be_sctr[kMaxCand][16], be_bits[kMaxCand][16],
         be_dist[kMaxCand][16];
+#endif
     alignas(16) int4 be_w[kMaxCand][16];  // packed block statistics (device path): w0, w1, w2 of eval_candidates, -
     // Per-step results are double-buffered by step parity (Ctx::par): after a
     // step's last barrier, waves still read its results (the candidate scan,
@@ -346,6 +395,10 @@ struct Shared {
     // VGPRs for the whole MB (which the compiler spilled to scratch: those
     // scratch stores were most of k_pipeline's HBM writes)
     LaneK lk[16];
+    // memo of eval_candidates' phase 1, empty at every MB start (mb_begin):
+    // x = key (0 = empty), y / z / w = the block's be_w words.  Last field:
+    // the register allocation follows the offsets of the fields above.
+    alignas(16) int4 memo[kMemoSlots];
 };
 
 // 8x8-family helper tasks (guess_inter): 1 = built in.  Off
@@ -893,6 +946,8 @@ __device__ __forceinline__ void mb_begin(Ctx& c)
     if (tid >= 256) S.ct.rb[(tid - 256) >> 4][tid & 15] = (uint8_t)b4;
     if (tid >= 240 && tid < 240 + 4 * 17) S.ct.tok3[(tid - 240) / 17][(tid - 240) % 17] = b5;
     if (tid >= kMbThreads - 48) (&S.be_tcm[0][0])[tid - (kMbThreads - 48)] = 0u;  // every slot empty at the MB start
+#pragma unroll
+    for (int t = tid; t < kMemoSlots; t += kMbThreads) S.memo[t].x = 0;  // the memo's keys: empty (never an epoch tag: a stale alias would be a silent wrong answer)
     if (tid >= 448 && tid < 464) {
         const int8_t* e = kQpelTab[tid - 448];
         const uint32_t q = (uint32_t)(e[0] | (e[1] << 2) | (e[2] << 3) | ((e[3] >= 0) << 4) | ((e[3] >= 0 ? e[3] : 0) << 5) | (e[4] << 7) | (e[5] << 8));
@@ -1031,6 +1086,10 @@ HD void mb_begin(Ctx& c)
     const int hasA = c.mbx > 0, hasB = c.mby > 0, hasC = c.mby > 0 && c.mbx < F.mbw - 1, hasD = c.mbx > 0 && c.mby > 0;
     const int addrs[5] = {a, a - 1, a - F.mbw, a - F.mbw + 1, a - F.mbw - 1};
     const int av[5] = {1, hasA, hasB, hasC, hasD};
+    for (int t = tid; t < kMemoSlots; t += nthr) S.memo[t].x = 0;  // the memo's keys: empty at the MB start
+#if defined(HL_EMU_BUILD) && !defined(__HIP_DEVICE_COMPILE__)
+    g_emu_memo_mb = -1;  // (no evaluation yet)
+#endif
 #if defined(__HIP_DEVICE_COMPILE__)
     coop_tables_init(S.ct, tid, nthr);
     for (int t = tid; t < 48; t += nthr) (&S.be_tcm[0][0])[t] = 0u;  // every slot empty at the MB start
@@ -1230,7 +1289,8 @@ HD void put_cand(Ctx& c, int xo, int yo, int pw, int pht, int i, int mx, int my,
 #endif
     cs.mvx = (int16_t)mx;
     cs.mvy = (int16_t)my;
-    cs.pad = pt;  // diamond point index
+    // diamond point index; the memo key's candidate part: phase and clamped displacement
+    cs.pad = pt | (int)(memo_kbase(X - kPad - (c.xL + xo), Y - kPad - (c.yL + yo), ph) << 4);
     (void)pw;
     (void)pht;
     if (writer) c.S.wc[c.tid >> 6][i] = cs;
@@ -1267,6 +1327,7 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
     uint8_t(&tcb)[16][kMaxCand] = S.be_tcb[c.par];
     HL_PROF_T(tp0);
 #if defined(__HIP_DEVICE_COMPILE__)
+    int pend[kQPass];  // memo slots this lane claimed in this pass (-1: none)
     // phase 1: one 4-lane quad per (candidate, 4x4 block), lane r = block row
     // r (hl_quad.h); every quad issues its prediction loads for both rounds
     // before computing
@@ -1286,24 +1347,109 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
                 e = !((S.f3w >> ni) & 1);
                 return S.tc[ni];
             }, S.f3lo, S.f3hi);
-        int o1[kQPass], o2[kQPass];
-        uint32_t sv[kQPass], pr[kQPass];
+        // what a block's quad hands on (the quad's writer lane; every operand is
+        // uniform in the quad): its be_w words w0 = tc | t1 << 5 | (sctr + 1) << 8,
+        // w1 = rest | dist << 16, w2 = tok -- computed below or taken from the memo
+        auto emit = [&](int ci, int k, int w0, int w1, int w2) {
+            const int tc = w0 & 31, sctr = ((w0 >> 8) & 15) - 1, rest = w1 & 0xFFFF, dist = (int)((uint32_t)w1 >> 16);
+            S.be_w[ci][k] = make_int4(w0, w1, w2, 0);
+            tcb[k][ci] = (uint8_t)tc;
+            if (tc) atomicOr(&S.be_tcm[c.p3][k], 1u << ci);
+            if (g.nblk == 1) {
+                // a single-block partition: both nC neighbours lie outside it, so the
+                // nC (and the candidate's cost) needs no other block (phase 2 skipped)
+                int bits = 0;
+                if (tc) bits = rest + ((w2 >> (5 * (nc1 < 2 ? 0 : (nc1 < 4 ? 1 : (nc1 < 8 ? 2 : 3))))) & 31);
+                const CandSlot cs = S.wc[wave][ci];
+                R.cost[ci] = mv_cost(F, dist, bits, cs.mvx, cs.mvy, pmv);
+                R.bits[ci] = bits;
+                R.dist[ci] = dist;
+                R.single[ci] = tc ? sctr : 0;
+                R.cbp[ci] = tc ? 1 << blk_idx(g.px, g.py) : 0;
+                R.last[ci] = tc ? sctr : -1;
+            }
+        };
+        // The memo (Shared::memo; key layout at kMemoSlots).  Every quad probes
+        // for its blocks before the prediction loads: lane r reads slot
+        // (hash + r) of the key's probe window, one 16-byte read per lane; the
+        // lane that finds the key hands the stored words on (emit) and the
+        // quad neither loads nor computes.  A wave whose quads all hit goes
+        // straight to the pass barrier.  A quad that missed computes, and its
+        // lane 0 inserts.
+        // Waves are not synchronised inside phase 1, and a key can occur twice
+        // in one pass (a speculative chain), so a probe must never take an
+        // entry whose words are not all written.  Protocol: the inserter claims
+        // the first empty slot of the window with atomicCAS(key word, 0,
+        // key | kMemoPending) and then stores the three words; probes compare
+        // the whole key word, so a pending entry is a mismatch (that block is
+        // computed; its insert finds key | kMemoPending and leaves).  The
+        // inserter clears kMemoPending after the pass barrier below: the words
+        // were complete before the barrier, and no probe of this pass runs
+        // after it, so whoever sees the key without the mark sees the words.
+        // A probe of the next pass that still sees the mark misses, no more.
+        // Entries of earlier MBs are cleared by mb_begin, behind its barrier.
+        // A full window means "compute, don't insert": capacity moves speed,
+        // never bytes.  (The emulator makes an insert visible at the end of the
+        // pass too, so its counters are the device's.)
+        const int mslots = max(0, min(uni(F.memo), kMemoSlots)), mlg = mslots ? 31 - __clz(mslots) : 0;  // (every index below stays inside S.memo)
+        // The probe path is what most passes run and nothing else, and it is a
+        // chain of dependent instructions: the addresses, the source row and
+        // the loads of a block are left to the quads that missed, and a pass
+        // of one round (n <= nq, most passes) never looks at the second.
+        uint32_t mkey[kQPass], mex[kQPass];  // the block's key (0: none), the key word its lane probed
+        bool miss[kQPass];
 #pragma unroll
         for (int j = 0; j < kQPass; ++j) {
-            const int item = min(qg + j * nq, n - 1);  // clamped: no divergence, valid addresses
-            const int ci = item >> g.lnb, k = item & (g.nblk - 1);
-            const int hx = k & (g.nbw - 1), hy = k >> g.lbw;
-            const int2 cs = *reinterpret_cast<const int2*>(&S.wc[wave][ci]);
-            const int o = ((hy << 2) + Q.r) * F.pstride + (hx << 2);
-            o1[j] = cs.x + o;
-            o2[j] = cs.y + o;
-            sv[j] = *reinterpret_cast<const uint32_t*>(&S.src[(g.py + (hy << 2) + Q.r) * 16 + g.px + (hx << 2)]);
+            mkey[j] = mex[j] = 0u;
+            miss[j] = false;
+            pend[j] = -1;
+            if (j * nq < n) {  // (uniform)
+                const bool live = qg + j * nq < n;
+                miss[j] = live;
+                if (mslots) {
+                    static_assert(kMemoProbe == 4, "one slot of the probe window per lane of the quad");
+                    const int item = min(qg + j * nq, n - 1);
+                    const int ci = item >> g.lnb, k = item & (g.nblk - 1);
+                    const int hx = k & (g.nbw - 1), hy = k >> g.lbw;
+                    const uint32_t kb = (uint32_t)S.wc[wave][ci].pad >> 4;  // 0: the displacement does not fit (bypass)
+                    mkey[j] = live && kb ? memo_key(kb, (((g.py >> 2) + hy) << 2) + (g.px >> 2) + hx) : 0u;
+                    const int4 e = S.memo[(memo_hash(mkey[j], mlg) + Q.r) & (mslots - 1)];
+                    const bool match = mkey[j] != 0u && (uint32_t)e.x == mkey[j];
+                    const uint32_t mq = (uint32_t)(__ballot(match) >> (c.tid & 60)) & 15u;  // the quad's lanes that found the key
+                    if (match && !(mq & ((1u << Q.r) - 1u))) emit(ci, k, e.y, e.z, e.w);
+                    miss[j] = live && !mq;
+                    mex[j] = (uint32_t)e.x;
+                }
+            }
         }
+        bool anymiss = false;
+#pragma unroll
+        for (int j = 0; j < kQPass; ++j) anymiss = anymiss || miss[j];
+#if defined(HL_PROF_MISC)
+        if (!F.early_term) {  // (slot 12 times early termination's homogeneity otherwise)
+            c.pacc[12] += __ballot(anymiss) == 0;  // wave 0's passes that skipped the quad rounds (tools/pipe_profile.py)
+            c.pcnt[12] += 1;
+        }
+#endif
         HL_PROF_T(ta0);
+        if (__ballot(anymiss) != 0) {
+        uint32_t sv[kQPass], pr[kQPass];
+        int mins[kQPass];  // first position of the window worth a claim (kMemoProbe: none)
         {
 #pragma unroll
             for (int j = 0; j < kQPass; ++j)
-                if (qg + j * nq < n) pr[j] = avg_u8x4(ld_u8x4(base, o1[j]), ld_u8x4(base, o2[j]));
+                if (miss[j]) {  // every quad that missed issues its prediction loads for both rounds before computing
+                    const int item = qg + j * nq;
+                    const int ci = item >> g.lnb, k = item & (g.nblk - 1);
+                    const int hx = k & (g.nbw - 1), hy = k >> g.lbw;
+                    const int2 cs = *reinterpret_cast<const int2*>(&S.wc[wave][ci]);
+                    const int o = ((hy << 2) + Q.r) * F.pstride + (hx << 2);
+                    sv[j] = *reinterpret_cast<const uint32_t*>(&S.src[(g.py + (hy << 2) + Q.r) * 16 + g.px + (hx << 2)]);
+                    pr[j] = avg_u8x4(ld_u8x4(base, cs.x + o), ld_u8x4(base, cs.y + o));
+                    // (the whole quad is here: its lanes' view of the window)
+                    const uint32_t uq = (uint32_t)(__ballot(mex[j] == 0u || (mex[j] & ~kMemoPending) == mkey[j]) >> (c.tid & 60)) & 15u;
+                    mins[j] = uq ? __ffs(uq) - 1 : kMemoProbe;
+                }
         }
 #if defined(HL_STEP_PROF)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the loads' latency (profiling only)
@@ -1313,7 +1459,7 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
 #pragma unroll
         for (int j = 0; j < kQPass; ++j) {
             const int item = qg + j * nq;
-            if (item < n) {
+            if (miss[j]) {
 #if defined(HL_NOP_PROBE)  // timing experiment: HL_NOP_PROBE x 8 independent VALU issue slots per quad round
 #pragma unroll
                 for (int np = 0; np < HL_NOP_PROBE; ++np) asm volatile("v_nop\n v_nop\n v_nop\n v_nop\n v_nop\n v_nop\n v_nop\n v_nop");
@@ -1343,21 +1489,22 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
                     if (Q.r == 0 && st.tc) tok = (int)S.ct.tok3[st.t1][st.tc];  // coeff_token lengths for the four nC classes
                 }
                 if (Q.r == 0) {
-                    S.be_w[ci][k] = make_int4(st.tc | (st.t1 << 5) | ((st.sctr + 1) << 8), st.rest | (dist << 16), tok, 0);
-                    tcb[k][ci] = (uint8_t)st.tc;
-                    if (st.tc) atomicOr(&S.be_tcm[c.p3][k], 1u << ci);
-                    if (g.nblk == 1) {
-                        // a single-block partition: both nC neighbours lie outside it, so the
-                        // nC (and the candidate's cost) needs no other block (phase 2 skipped)
-                        int bits = 0;
-                        if (st.tc) bits = st.rest + ((tok >> (5 * (nc1 < 2 ? 0 : (nc1 < 4 ? 1 : (nc1 < 8 ? 2 : 3))))) & 31);
-                        const CandSlot cs = S.wc[wave][ci];
-                        R.cost[ci] = mv_cost(F, dist, bits, cs.mvx, cs.mvy, pmv);
-                        R.bits[ci] = bits;
-                        R.dist[ci] = dist;
-                        R.single[ci] = st.tc ? st.sctr : 0;
-                        R.cbp[ci] = st.tc ? 1 << blk_idx(g.px, g.py) : 0;
-                        R.last[ci] = st.tc ? st.sctr : -1;
+                    const int w0 = st.tc | (st.t1 << 5) | ((st.sctr + 1) << 8), w1 = st.rest | (dist << 16);
+                    emit(ci, k, w0, w1, tok);
+                    if (mkey[j]) {  // claim the first slot of the window that is still empty, unless the key is there
+                        int slot = -1;
+                        for (int p = mins[j]; p < kMemoProbe; ++p) {
+                            const int ix = (memo_hash(mkey[j], mlg) + p) & (mslots - 1);
+                            const uint32_t old = atomicCAS(reinterpret_cast<uint32_t*>(&S.memo[ix].x), 0u, mkey[j] | kMemoPending);
+                            if (old == 0u) slot = ix;
+                            if (old == 0u || (old & ~kMemoPending) == mkey[j]) break;
+                        }
+                        if (slot >= 0) {
+                            S.memo[slot].y = w0;
+                            S.memo[slot].z = w1;
+                            S.memo[slot].w = tok;
+                        }
+                        pend[j] = slot;
                     }
                 }
             }
@@ -1365,6 +1512,7 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
 #if defined(HL_STEP_PROF)
         HL_PROF_ADD(c, 13, ta1);
 #endif
+        }  // (a wave with a miss)
     }
 #if defined(HL_STEP_PROF)
     HL_PROF_T(tb0);
@@ -1378,6 +1526,10 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
     // and commit of the pass before this one) are done, and its first
     // writer runs after the next pass's barrier above
     if (c.tid < 16) S.be_tcm[c.p3 == 0 ? 2 : c.p3 - 1][c.tid] = 0;
+    // this pass's memo entries become visible (see the protocol above)
+#pragma unroll
+    for (int j = 0; j < kQPass; ++j)
+        if (pend[j] >= 0) atomicAnd(reinterpret_cast<uint32_t*>(&S.memo[pend[j]].x), ~kMemoPending);
 #endif
 #if defined(HL_NBLK_PROF)  // phase 1 by partition size: slots 12..15 = 1, 2, 4, 8+ blocks
     HL_PROF_ADD(c, 12 + (g.nblk >= 8 ? 3 : g.lnb), tp0);
@@ -1511,10 +1663,52 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
 #else
     HL_PROF_T(tp2);
     const int n = ncand * g.nblk;
-    // phase 1: transform / quant / CAVLC statistics / reconstruction per block
+    // phase 1: transform / quant / CAVLC statistics / reconstruction per block,
+    // through the memo with the device path's semantics (see there): same key,
+    // same hash and probe window, an insert visible from the end of the pass
+#if defined(HL_EMU_BUILD)
+    const int mslots = g_emu_memo_slots;  // the emulator's setting is a host global (emu_set_memo), like g_emu_bad_guess
+#else
+    const int mslots = F.memo < 0 ? 0 : (F.memo < kMemoSlots ? F.memo : kMemoSlots);
+#endif
+    int mlg = 0;
+    while (mslots >> (mlg + 1)) ++mlg;
+    int mprobe = kMemoProbe;
+    int mpend[kMaxCand * 16], npend = 0;
+#if defined(HL_EMU_BUILD)
+    mprobe = g_emu_memo_probe;
+    if (g_emu_memo_mb < 0) {
+        g_emu_memo_mb = 0;
+        ++g_emu_memo_stat[MS_MBS];
+    }
+    unsigned long long wmiss = 0;  // 16-item groups of the pass (a wave's share of a 128-item round) with a miss
+#endif
     for (int t = c.tid; t < n; t += c.nthr) {
         const int ci = t / g.nblk, k = t % g.nblk;
         const int hx = k % g.nbw, hy = k / g.nbw;
+        const uint32_t kb = mslots ? (uint32_t)S.wc[0][ci].pad >> 4 : 0u;  // 0: the displacement does not fit (bypass)
+        const uint32_t mkey = kb ? memo_key(kb, (((g.py >> 2) + hy) << 2) + (g.px >> 2) + hx) : 0u;
+        const int mh = memo_hash(mkey, mlg);
+        bool hit = false;
+        for (int p = 0; mkey && p < mprobe && !hit; ++p) {
+            const int4& e = S.memo[(mh + p) & (mslots - 1)];
+            if ((uint32_t)e.x == mkey) {
+                hit = true;
+                S.be_tc[ci][k] = e.y & 31;
+                S.be_nz[ci][k] = (e.y & 31) != 0;
+                S.be_t1[ci][k] = (e.y >> 5) & 7;
+                S.be_sctr[ci][k] = ((e.y >> 8) & 15) - 1;
+                S.be_bits[ci][k] = e.z & 0xFFFF;
+                S.be_dist[ci][k] = (int)((uint32_t)e.z >> 16);
+            }
+        }
+#if defined(HL_EMU_BUILD)
+        ++g_emu_memo_stat[MS_ITEMS];
+        g_emu_memo_stat[MS_HITS] += hit;
+        g_emu_memo_stat[MS_BYPASSED] += mslots && !kb;
+        if (!hit) wmiss |= 1ull << (t >> 4);
+#endif
+        if (hit) continue;
         const int mvx = S.wc[0][ci].mvx, mvy = S.wc[0][ci].mvy;
         const int X = clip3(-17, F.W + 17, c.xL + g.px + (mvx >> 2)) + (hx << 2);
         const int Y = clip3(-17, F.H + 17, c.yL + g.py + (mvy >> 2)) + (hy << 2);
@@ -1554,7 +1748,41 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
         S.be_sctr[ci][k] = st.sctr;
         S.be_bits[ci][k] = st.rest;
         S.be_dist[ci][k] = dist;
+        if (mkey) {  // claim the first slot of the window that is empty, unless the key is there (pending)
+            int slot = -1, p = 0;
+            for (; p < mprobe; ++p) {
+                const int ix = (mh + p) & (mslots - 1);
+                const uint32_t old = (uint32_t)S.memo[ix].x;
+                if (old == 0u) slot = ix;
+                if (old == 0u || (old & ~kMemoPending) == mkey) break;
+            }
+            if (slot >= 0) {
+                S.memo[slot] = make_int4((int)(mkey | kMemoPending), st.tc | (st.t1 << 5) | ((st.sctr + 1) << 8), st.rest | (dist << 16), 0);
+                mpend[npend++] = slot;
+            }
+#if defined(HL_EMU_BUILD)
+            if (slot >= 0 || p == mprobe) {
+                g_emu_memo_stat[slot >= 0 ? MS_INSERTED : MS_NOT_INSERTED]++;
+                if (++g_emu_memo_mb > g_emu_memo_stat[MS_MB_KEYS_MAX]) g_emu_memo_stat[MS_MB_KEYS_MAX] = g_emu_memo_mb;
+            }
+#endif
+        }
     }
+    for (int i = 0; i < npend; ++i) S.memo[mpend[i]].x &= (int)~kMemoPending;  // visible from the next pass on
+#if defined(HL_EMU_BUILD)
+    {
+        const int rounds = (n + 127) / 128, wr = (n + 15) / 16;
+        int rm = 0, wm = 0;
+        for (int r = 0; r < rounds; ++r) rm += ((wmiss >> (r * 8)) & 0xFF) != 0;
+        for (int w = 0; w < wr; ++w) wm += (int)((wmiss >> w) & 1);
+        ++g_emu_memo_stat[MS_PASSES];
+        g_emu_memo_stat[MS_PASSES_ALL_HIT] += rm == 0;
+        g_emu_memo_stat[MS_ROUNDS] += rounds;
+        g_emu_memo_stat[MS_ROUNDS_MISS] += rm;
+        g_emu_memo_stat[MS_WAVE_ROUNDS] += wr;
+        g_emu_memo_stat[MS_WAVE_ROUNDS_MISS] += wm;
+    }
+#endif
     // phase 2: nC as the reference sees it at this point of the sequence
     for (int t = c.tid; t < n; t += c.nthr) {
         const int ci = t / g.nblk, k = t % g.nblk;
@@ -1892,7 +2120,7 @@ HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
         b.cbp = uni(S.cd[c.par].cbp[bi]);
         b.mv[0] = uni((int)S.wc[c.tid >> 6][bi].mvx);
         b.mv[1] = uni((int)S.wc[c.tid >> 6][bi].mvy);
-        return uni(S.wc[c.tid >> 6][bi].pad);
+        return uni(S.wc[c.tid >> 6][bi].pad & 15);
     };
     auto pick = [&](int lo, int hi, double& m) -> int { return pick_first_min(c, lo, hi, m); };
 #endif
@@ -1995,7 +2223,7 @@ HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
             pv_last = R.last[l];
             pv_mvx = cs.mvx;
             pv_mvy = cs.mvy;
-            pv_pad = cs.pad;
+            pv_pad = cs.pad & 15;
         }
         // The sequential strict-< scans of every step of the chain
         // (me_ds.c:339-347) at once: four independent DPP minimum chains over

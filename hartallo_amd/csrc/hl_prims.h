@@ -127,8 +127,8 @@ HD int tc0_of(int indexA, int bS) { return kTc0[indexA][bS - 1]; }
 
 // lambda_mode = HL_CODEC_264_RDO_LAMBDA_FACT_ALL * (1 << ((QP - 12) / 3)) as
 // the reference's x86 build computes it (slice.c:1766): the int shift count
-// is negative below QP 10, and x86's SHL uses its low 5 bits -- QP 0-2 give
-// 2^28 / 2^29, QP 3-6 2^30, QP 7-9 (int)(1u << 31) = INT_MIN, a negative
+// is negative below QP 10, and x86's SHL uses its low 5 bits -- QP 0 gives
+// 2^28, QP 1-3 2^29, QP 4-6 2^30, QP 7-9 (int)(1u << 31) = INT_MIN, a negative
 // lambda.  Written with that masking explicit (a negative shift count is
 // undefined in C++).
 HD double rdo_lambda(int qp) { return 0.852 * (double)(int32_t)(1u << (((qp - 12) / 3) & 31)); }

@@ -80,7 +80,11 @@ typedef struct hl_amd_result_s {
 
 typedef struct hl_amd_encoder_s hl_amd_encoder_t;
 
-/* hl_codec_create + option setting for HL_CODEC_TYPE_H264 (hl_codec.c:24-150) */
+/* hl_codec_create + option setting for HL_CODEC_TYPE_H264 (hl_codec.c:24-150).
+ * A/B knob read here: HL_AMD_MEMO -- the memo of the per-block candidate
+ * evaluation: unset = the built capacity, 0 = off, N = N slots
+ * (a power of two up to the capacity; anything else: INVALID_PARAMETER).
+ * Results do not depend on it. */
 int32_t hl_amd_encoder_create(const hl_amd_params_t* params, hl_amd_encoder_t** encoder);
 void hl_amd_encoder_destroy(hl_amd_encoder_t* encoder);
 

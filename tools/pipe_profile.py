@@ -85,9 +85,13 @@ def main():
         for name, v in (("task-start waits", wait), ("decisions", mb), ("deblock + planes", filt), ("intra helpers", hlp),
                         ("rest", life - wait - mb - filt - hlp)):
             print(f"   {name:18s} {100.0 * v / life:6.1f} %   {v / max(1, tasks) / 1e3:9.1f} kcycles/task")
+    default_build = not any(os.environ.get(k) for k in ("HL_I4_NAMES", "HL_STEP_NAMES"))
+    if default_build and cnt[25]:  # slot 12 of the default profiling build: wave 0's evaluation passes / those whose quads all hit the memo
+        print(f"   eval:memo          wave 0 skipped the quad rounds in {cnt[24]} of {cnt[25]} passes ({100.0 * cnt[24] / cnt[25]:.1f} %; "
+              f"{cnt[25] / (n * nmb):.1f} passes/MB)")
     for i, name in enumerate(PHASES):
         cyc, calls = cnt[2 * i], cnt[2 * i + 1]
-        if calls and name:
+        if calls and name and not (default_build and i == 12):  # (no early termination here: the slot counts the memo's skips, above)
             print(f"   {name:18s} calls/MB {calls / (n * nmb):8.1f}  cycles/call {cyc / calls:10.0f}  kcycles/MB {cyc / (n * nmb) / 1e3:9.1f}")
     if nsites:  # barrier sites by their wait (source line = 2 * site or 2 * site + 1, any header)
         base = 64 + 4 * nmb
