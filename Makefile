@@ -6,6 +6,7 @@
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := hartallo_amd/csrc
+REF     ?= /root/reference
 HDRS    := $(wildcard $(CSRC)/*.h) include/hartallo_amd.h
 HOSTSRC := $(CSRC)/hl_writer.cpp $(CSRC)/hl_rc.cpp
 # the product kernels, and k_pipeline again with the 8x8-family helpers (runs of one picture)
@@ -27,9 +28,11 @@ unit: tests/gpu_unit/libhl_unit.so
 hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -shared -o $@ $(KSRC) $(HOSTSRC)
 
-# (hl_emu_memo.hip = hl_emu.hip plus the memo's settings, counters and key export)
-EMUSRC := tests/emu/hl_emu_memo.hip
-tests/emu/libhl_emu.so: $(EMUSRC) tests/emu/hl_emu.hip $(HOSTSRC) $(HDRS)
+# (hl_emu_ctl.hip = hl_emu_memo.hip plus emu_encode_frame_ex; hl_emu_memo.hip =
+# hl_emu.hip plus the memo's settings, counters and key export)
+EMUSRC := tests/emu/hl_emu_ctl.hip
+EMUINC := tests/emu/hl_emu_memo.hip tests/emu/hl_emu.hip
+tests/emu/libhl_emu.so: $(EMUSRC) $(EMUINC) $(HOSTSRC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -O2 -DHL_FAM3=1 -shared -o $@ $(EMUSRC) $(HOSTSRC)
 
 tests/gpu_unit/libhl_unit.so: tests/gpu_unit/hl_unit.hip $(HDRS)
@@ -51,7 +54,7 @@ tests/sanitize/hl_writer_asan.o: $(CSRC)/hl_writer.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) $(ASAN) $(UBSAN) -c -o $@ $<
 tests/sanitize/hl_rc_asan.o: $(CSRC)/hl_rc.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) $(ASAN) $(UBSAN) -c -o $@ $<
-tests/sanitize/hl_emu_asan.o: $(EMUSRC) tests/emu/hl_emu.hip $(HDRS)
+tests/sanitize/hl_emu_asan.o: $(EMUSRC) $(EMUINC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) -DHL_FAM3=1 $(ASAN) -c -o $@ $<
 tests/sanitize/libhl_emu_asan.so: tests/sanitize/hl_emu_asan.o tests/sanitize/hl_writer_asan.o tests/sanitize/hl_rc_asan.o
 	$(HIPCC) --offload-arch=$(ARCH) $(ASAN) $(UBSAN) -shared-libsan -shared -o $@ $^
@@ -61,7 +64,7 @@ tests/sanitize/rowgate_tsan: tests/sanitize/rowgate_tsan.cpp $(CSRC)/hl_writer.c
 # the kernel logic, run once per change of the shift / overflow idioms
 # (DESIGN.md §2); tests/test_sanitizers.py uses it when it is present
 ubsan: tests/sanitize/libhl_emu_ubsan.so
-tests/sanitize/libhl_emu_ubsan.so: $(EMUSRC) tests/emu/hl_emu.hip $(HOSTSRC) $(HDRS)
+tests/sanitize/libhl_emu_ubsan.so: $(EMUSRC) $(EMUINC) $(HOSTSRC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) -DHL_FAM3=1 $(ASAN) $(UBSAN) -shared-libsan -shared -o $@ $(EMUSRC) $(HOSTSRC)
 
 # profiling build: same library (same device scheduling flags) with per-phase
@@ -93,8 +96,10 @@ build/$(V)/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
 	mkdir -p build/$(V)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) $(VDEFS) -shared -o $@ $(KSRC) $(HOSTSRC)
 
+# (then the drivers with a per-frame schedule, tests/refdrive, where the reference library was built)
 oracle: product  # oracle/_ref/drop_in_enc links the product library
 	$(MAKE) -C oracle
+	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
 	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/gpu_unit/libhl_unit.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan

@@ -6,12 +6,13 @@ with the reference encoder, behind a
 C ABI (include/hartallo_amd.h) that a hartallo plugin forwards to.
 """
 from ._lib import (EXPORTED_SYMBOLS, HL_AMD_RESULT_TYPE_DATA, HL_AMD_RESULT_TYPE_HDR, LIB_PATH, EncodeResult, Encoder,
-                   HlAmdError, SvcEncoder, load_library)
+                   FrameCtl, HlAmdError, SvcEncoder, load_library)
 
 __all__ = [
     "Encoder",
     "SvcEncoder",
     "EncodeResult",
+    "FrameCtl",
     "HlAmdError",
     "load_library",
     "LIB_PATH",

@@ -26,6 +26,12 @@ HL_AMD_ERROR_SYSTEM = 13
 HL_AMD_ERROR_TOOSHORT = 15
 HL_AMD_RESULT_TYPE_DATA = 1
 HL_AMD_RESULT_TYPE_HDR = 2
+# HL_AMD_ENCODING_* (= HL_VIDEO_ENCODING_TYPE_T, hl_types.h:262-274)
+HL_AMD_ENCODING_AUTO = 0
+HL_AMD_ENCODING_INTRA = 1
+HL_AMD_ENCODING_INTER = 2
+HL_AMD_ENCODING_LOSSLESS = 3
+HL_AMD_ENCODING_RAW = 4
 
 # every symbol include/hartallo_amd.h declares
 EXPORTED_SYMBOLS = (
@@ -37,6 +43,10 @@ EXPORTED_SYMBOLS = (
     "hl_amd_encode_device",
     "hl_amd_encode_batch",
     "hl_amd_encode_streams",
+    "hl_amd_encode_ex",
+    "hl_amd_encode_device_ex",
+    "hl_amd_encode_batch_ex",
+    "hl_amd_encode_streams_ex",
     "hl_amd_set_pipeline",
     "hl_amd_set_rate_control",
     "hl_amd_set_max_ref_frame",
@@ -90,6 +100,36 @@ class _Result(ctypes.Structure):
         ("data", ctypes.c_void_p),
         ("data_size", ctypes.c_size_t),
     ]
+
+
+class _FrameCtl(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("encoding", "me_range", "deblock", "me_early_term", "gop_size")]
+
+
+@dataclass
+class FrameCtl:
+    """hl_amd_frame_ctl_t: what the reference reads on every encode call
+    beside the planes -- hl_frame_t.encoding (HL_AMD_ENCODING_*) and the
+    hl_codec_t settings at the time of the call, which stay until the next
+    change (include/hartallo_amd.h)."""
+
+    encoding: int = HL_AMD_ENCODING_AUTO
+    me_range: int = 16
+    deblock: int = 1
+    me_early_term: int = 0
+    gop_size: int = 30
+
+    def _c(self) -> _FrameCtl:
+        return _FrameCtl(self.encoding, self.me_range, self.deblock, self.me_early_term, self.gop_size)
+
+
+def _ctl_array(ctls, n):
+    """n FrameCtl objects as a C array (None: no ctl for the call)."""
+    if ctls is None:
+        return None
+    if len(ctls) != n:
+        raise HlAmdError(HL_AMD_ERROR_INVALID_PARAMETER, "ctl (one per frame)")
+    return (_FrameCtl * n)(*[c._c() for c in ctls])
 
 
 def _mb_record_dtype():
@@ -173,6 +213,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "hl_amd_encode_streams"):  # (absent from builds before round 4 loaded through HL_LIB)
         lib.hl_amd_encode_streams.argtypes = [ctypes.POINTER(vp), i32, i32, pp, pp, pp, ctypes.POINTER(_Result)]
         lib.hl_amd_encode_streams.restype = i32
+    pc = ctypes.POINTER(_FrameCtl)
+    for f in (lib.hl_amd_encode_ex, lib.hl_amd_encode_device_ex):
+        f.argtypes = [vp, vp, vp, vp, pc, ctypes.POINTER(_Result)]
+        f.restype = i32
+    lib.hl_amd_encode_batch_ex.argtypes = [vp, i32, pp, pp, pp, pc, ctypes.POINTER(_Result)]
+    lib.hl_amd_encode_batch_ex.restype = i32
+    lib.hl_amd_encode_streams_ex.argtypes = [ctypes.POINTER(vp), i32, i32, pp, pp, pp, pc, ctypes.POINTER(_Result)]
+    lib.hl_amd_encode_streams_ex.restype = i32
     lib.hl_amd_set_pipeline.argtypes = [vp, i32, i32, i32]
     lib.hl_amd_set_pipeline.restype = i32
     lib.hl_amd_set_rate_control.argtypes = [vp, ctypes.c_int64, i32, i32, i32, i32, i32]
@@ -286,17 +334,23 @@ class Encoder:
         hdr = ctypes.string_at(r.hdr, r.hdr_size) if r.type & HL_AMD_RESULT_TYPE_HDR else b""
         return EncodeResult(r.type, data, hdr)
 
-    def encode(self, y, u, v) -> EncodeResult:
-        """Encodes planar YUV420 from host memory (numpy uint8 arrays)."""
+    def encode(self, y, u, v, ctl: "FrameCtl | None" = None) -> EncodeResult:
+        """Encodes planar YUV420 from host memory (numpy uint8 arrays); ctl:
+        the frame's encoding type and the settings from this frame on
+        (hl_amd_encode_ex)."""
         import numpy as np
 
         ys = [np.ascontiguousarray(p, dtype=np.uint8) for p in (y, u, v)]
         if ys[0].size != self.width * self.height or ys[1].size != self.width * self.height // 4 or ys[2].size != ys[1].size:
             raise HlAmdError(HL_AMD_ERROR_INVALID_FORMAT, "encode (plane sizes)")
         r = _Result()
-        rc = self.lib.hl_amd_encode(self._h, ys[0].ctypes.data, ys[1].ctypes.data, ys[2].ctypes.data, ctypes.byref(r))
+        if ctl is None:
+            rc = self.lib.hl_amd_encode(self._h, ys[0].ctypes.data, ys[1].ctypes.data, ys[2].ctypes.data, ctypes.byref(r))
+        else:
+            rc = self.lib.hl_amd_encode_ex(self._h, ys[0].ctypes.data, ys[1].ctypes.data, ys[2].ctypes.data, ctypes.byref(ctl._c()),
+                                           ctypes.byref(r))
         if rc != HL_AMD_SUCCESS:
-            raise HlAmdError(rc, "hl_amd_encode")
+            raise HlAmdError(rc, "hl_amd_encode" if ctl is None else "hl_amd_encode_ex")
         return self._result(r)
 
     def set_lookahead(self, frames: int) -> None:
@@ -317,34 +371,45 @@ class Encoder:
             raise HlAmdError(rc, "hl_amd_flush")
         return self._result(r)
 
-    def encode_device(self, y_ptr: int, u_ptr: int, v_ptr: int, collect: bool = True):
-        """Encodes planes already resident in device memory (raw pointers)."""
+    def encode_device(self, y_ptr: int, u_ptr: int, v_ptr: int, collect: bool = True, ctl: "FrameCtl | None" = None):
+        """Encodes planes already resident in device memory (raw pointers);
+        ctl as in encode (hl_amd_encode_device_ex)."""
         r = _Result()
-        rc = self.lib.hl_amd_encode_device(self._h, ctypes.c_void_p(y_ptr), ctypes.c_void_p(u_ptr), ctypes.c_void_p(v_ptr), ctypes.byref(r))
+        planes = (ctypes.c_void_p(y_ptr), ctypes.c_void_p(u_ptr), ctypes.c_void_p(v_ptr))
+        if ctl is None:
+            rc = self.lib.hl_amd_encode_device(self._h, *planes, ctypes.byref(r))
+        else:
+            rc = self.lib.hl_amd_encode_device_ex(self._h, *planes, ctypes.byref(ctl._c()), ctypes.byref(r))
         if rc != HL_AMD_SUCCESS:
-            raise HlAmdError(rc, "hl_amd_encode_device")
+            raise HlAmdError(rc, "hl_amd_encode_device" if ctl is None else "hl_amd_encode_device_ex")
         return self._result(r) if collect else r.data_size
 
-    def encode_batch_device(self, ptrs, collect: bool = True):
+    def encode_batch_device(self, ptrs, collect: bool = True, ctl=None):
         """Encodes consecutive frames already resident in device memory;
         ptrs = [(y_ptr, u_ptr, v_ptr), ...].  Runs of P pictures are
         frame-pipelined (hl_amd_encode_batch); returns one result per frame
-        (or, with collect=False, the total bitstream bytes)."""
+        (or, with collect=False, the total bitstream bytes).  ctl: one
+        FrameCtl per frame (hl_amd_encode_batch_ex); a forced IDR or a
+        changed setting stays inside the pipelined run."""
         n = len(ptrs)
         arr = [(ctypes.c_void_p * n)(*[p[i] for p in ptrs]) for i in range(3)]
         res = (_Result * n)()
-        rc = self.lib.hl_amd_encode_batch(self._h, n, arr[0], arr[1], arr[2], res)
+        if ctl is None:
+            rc = self.lib.hl_amd_encode_batch(self._h, n, arr[0], arr[1], arr[2], res)
+        else:
+            rc = self.lib.hl_amd_encode_batch_ex(self._h, n, arr[0], arr[1], arr[2], _ctl_array(ctl, n), res)
         if rc != HL_AMD_SUCCESS:
-            raise HlAmdError(rc, "hl_amd_encode_batch")
+            raise HlAmdError(rc, "hl_amd_encode_batch" if ctl is None else "hl_amd_encode_batch_ex")
         self._last_batch = res  # the results stay valid until the next encode call
         return [self._result(r) for r in res] if collect else sum(r.data_size for r in res)
 
     @staticmethod
-    def encode_streams_device(encoders, ptrs, collect: bool = True):
+    def encode_streams_device(encoders, ptrs, collect: bool = True, ctl=None):
         """hl_amd_encode_streams: frames of several streams in shared
         pipelined runs; encoders[s] codes ptrs[s] (each a list of (y, u, v)
         device pointers, the same length).  Returns per stream its results (or,
-        with collect=False, its total bitstream bytes)."""
+        with collect=False, its total bitstream bytes).  ctl: per stream a
+        list of one FrameCtl per frame (hl_amd_encode_streams_ex)."""
         S, n = len(encoders), len(ptrs[0])
         assert len(ptrs) == S and all(len(p) == n for p in ptrs)
         lib = encoders[0].lib
@@ -352,9 +417,16 @@ class Encoder:
         flat = [f for p in ptrs for f in p]
         arr = [(ctypes.c_void_p * (S * n))(*[f[i] for f in flat]) for i in range(3)]
         res = (_Result * (S * n))()
-        rc = lib.hl_amd_encode_streams(hs, S, n, arr[0], arr[1], arr[2], res)
+        if ctl is None:
+            rc = lib.hl_amd_encode_streams(hs, S, n, arr[0], arr[1], arr[2], res)
+        else:
+            if len(ctl) != S:
+                raise HlAmdError(HL_AMD_ERROR_INVALID_PARAMETER, "ctl (one list per stream)")
+            for c in ctl:
+                _ctl_array(c, n)  # (one per frame)
+            rc = lib.hl_amd_encode_streams_ex(hs, S, n, arr[0], arr[1], arr[2], _ctl_array([c for cs in ctl for c in cs], S * n), res)
         if rc != HL_AMD_SUCCESS:
-            raise HlAmdError(rc, "hl_amd_encode_streams")
+            raise HlAmdError(rc, "hl_amd_encode_streams" if ctl is None else "hl_amd_encode_streams_ex")
         out = []
         for s, e in enumerate(encoders):
             rs = res[s * n:(s + 1) * n]

@@ -915,8 +915,34 @@ constexpr int kProfExtra = 0;
 #endif
 constexpr int kRowsAt = 16;   // h_progress word of picture 0's row count
 
+// One picture's type and settings, decided as the reference does at the top of
+// its encode call from hl_frame_t.encoding and the hl_codec_t fields of that
+// moment (hl_amd_frame_ctl_t).
+struct PicPlan {
+    int32_t intra, me_range, deblock, early_term;
+};
+
+// The call's ctl (null: AUTO, nothing changes) applied to the live settings
+// and the GOP counter: a counter that has run out gives an IDR whatever is
+// asked and reloads, INTRA elsewhere forces one and reloads, AUTO and INTER
+// give a P picture (hl_codec_264.c:705-718); gop_size is read only at a
+// reload (:709, :717).  The caller decrements the counter after the picture
+// (:1004).
+static PicPlan plan_picture(hl_amd_params_t& live, int32_t& gop_left, const hl_amd_frame_ctl_t* c)
+{
+    if (c) {
+        live.me_range = c->me_range;
+        live.deblock = c->deblock;
+        live.me_early_term = c->me_early_term;
+        live.gop_size = c->gop_size;
+    }
+    const bool intra = gop_left <= 0 || (c && c->encoding == HL_AMD_ENCODING_INTRA);
+    if (intra) gop_left = live.gop_size;
+    return PicPlan{intra, std::min(64, std::max(1, live.me_range)) /* rdo.c:847 */, live.deblock != 0, live.me_early_term != 0};
+}
+
 struct hl_amd_encoder_s {
-    hl_amd_params_t p;
+    hl_amd_params_t p;  // me_range, deblock, me_early_term, gop_size: the live values (the last ctl's)
     int W, H, Wc, Hc, mbw, mbh, nmb, qpc, pstride;
     hipStream_t stream;
     uint8_t* d_in[3];
@@ -966,7 +992,8 @@ struct hl_amd_encoder_s {
     int nwriters;                            // host slice writer threads of a run
     int32_t max_ref_frame = 1;               // hl_codec_t.max_ref_frame: SPS/PPS fields only (hl_amd_set_max_ref_frame)
     std::vector<std::vector<uint8_t>> wscratch, wout;
-    std::vector<int32_t> run_intra, run_idr_id;  // per picture of the run: IDR, idr_pic_id
+    std::vector<PicPlan> run_plan;               // per picture of the run: its type (IDR or P) and settings (plan_picture)
+    std::vector<int32_t> run_idr_id;             // per picture of the run: idr_pic_id
     std::vector<int32_t> run_qp;                 // per picture of the run: SliceQPY (rate control: one picture per run)
     std::vector<SliceBits> run_bits;             // per picture of the run: header / texture bits (rate control)
     // accounting of the last encode call (hl_amd_last_batch_stats)
@@ -995,6 +1022,8 @@ struct hl_amd_encoder_s {
     };
     int32_t lookahead = 1;
     uint8_t* d_la = nullptr;                     // [lookahead] frames, Y | U | V each
+    std::vector<hl_amd_frame_ctl_t> la_ctl;      // [lookahead] the queued frames' ctl (hl_amd_encode_ex)
+    std::vector<char> la_has_ctl;                // ... and whether the frame came with one
     int32_t la_n = 0;                            // frames queued, not yet coded
     std::vector<LaOut> la_out;                   // coded results not yet handed out, from la_head
     size_t la_head = 0;
@@ -1199,10 +1228,10 @@ static int validate_chain(hl_amd_encoder_t* e, int row0, int& chain_end)
 // qp_set >= 0: the picture's QP was already taken from the rate controller
 // (by the run that fell back); the picture's statistics still go back to it.
 static int32_t encode_frame(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t* u, const uint8_t* v, hl_amd_result_t* r,
-                            int qp_set = -1)
+                            int qp_set = -1, const hl_amd_frame_ctl_t* ctl = nullptr)
 {
-    const bool intra = e->gop_left <= 0;
-    if (intra) e->gop_left = e->p.gop_size;
+    const PicPlan plan = plan_picture(e->p, e->gop_left, ctl);
+    const bool intra = plan.intra != 0;
     // rate control picks the picture's QP before it is coded (hl_codec_264.c:719-742)
     const int qp = qp_set >= 0 ? qp_set : (e->rc ? e->rc->begin_picture(intra) : e->p.qp);
     const int qpc = kQpToQpc[qp];
@@ -1218,8 +1247,8 @@ static int32_t encode_frame(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t
     F.qp = qp;
     F.qpc = qpc;
     F.is_intra = intra;
-    F.me_range = std::min(64, std::max(1, e->p.me_range));
-    F.early_term = e->p.me_early_term != 0;
+    F.me_range = plan.me_range;
+    F.early_term = plan.early_term;
     F.memo = e->memo;
     F.lambda = rdo_lambda(qp);  // slice.c:1766
     F.src[0] = y;
@@ -1274,7 +1303,7 @@ static int32_t encode_frame(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t
     }
     e->chain_end = chain_end;
     if (e->timing) HL_HIP_CHECK(hipEventRecord(e->ev[2], e->stream));
-    if (e->p.deblock) {
+    if (plan.deblock) {
         DeblockArgs D;
         D.W = e->W;
         D.H = e->H;
@@ -1296,7 +1325,7 @@ static int32_t encode_frame(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t
         (void)hipEventElapsedTime(&e->ms[2], e->ev[2], e->ev[3]);
         (void)hipEventElapsedTime(&e->ms[3], e->ev[0], e->ev[3]);
     }
-    const StreamParams sp{e->W, e->H, e->p.qp, e->p.deblock};
+    const StreamParams sp{e->W, e->H, e->p.qp, plan.deblock};
     const SliceState ss{intra ? 1 : 0, e->pict_count, e->idr_pic_id, qp};
     SliceBits sb{};
     const size_t n = write_slice(sp, ss, e->h_rec, e->scratch.data(), e->out.data(), e->out.size(), &sb);
@@ -1443,7 +1472,7 @@ static bool validate_rows(const MbChain* ch, int mbw, int mbh, int spec, int32_t
     return true;
 }
 
-static FrameArgs frame_args(hl_amd_encoder_t* e, bool intra, int qp)
+static FrameArgs frame_args(hl_amd_encoder_t* e, const PicPlan& plan, int qp)
 {
     FrameArgs F{};
     F.W = e->W;
@@ -1454,9 +1483,9 @@ static FrameArgs frame_args(hl_amd_encoder_t* e, bool intra, int qp)
     F.mbh = e->mbh;
     F.qp = qp;
     F.qpc = kQpToQpc[qp];
-    F.is_intra = intra;
-    F.me_range = std::min(64, std::max(1, e->p.me_range));
-    F.early_term = e->p.me_early_term != 0;
+    F.is_intra = plan.intra != 0;
+    F.me_range = plan.me_range;
+    F.early_term = plan.early_term;
     F.memo = e->memo;
     F.lambda = rdo_lambda(qp);  // slice.c:1766
     F.pstride = e->pstride;
@@ -1480,7 +1509,7 @@ static void store_result(hl_amd_encoder_t* e, int i, const hl_amd_result_t& src,
 static std::vector<size_t> write_run(hl_amd_encoder_t* e, int m, int base, const std::atomic<bool>* abort = nullptr, int nw = 0)
 {
     const int n = std::max(1, std::min(m, nw > 0 ? nw : e->nwriters));
-    const StreamParams sp{e->W, e->H, e->p.qp, e->p.deblock};
+    const StreamParams sp{e->W, e->H, e->p.qp, 1};  // (buffer sizes; every picture's own below)
     if ((int)e->wscratch.size() < n) {
         e->wscratch.resize(n);
         e->wout.resize(n);
@@ -1511,11 +1540,13 @@ static std::vector<size_t> write_run(hl_amd_encoder_t* e, int m, int base, const
             Gate g{e->h_progress + kRowsAt + k, abort};
             const RowGate gate{&Gate::wait, &g};
             if (abort && !Gate::wait(&g, 0)) return;
-            const SliceState ss{e->run_intra[k], e->pict_count + k, e->run_idr_id[k], e->run_qp[k]};
+            const SliceState ss{e->run_plan[k].intra, e->pict_count + k, e->run_idr_id[k], e->run_qp[k]};
             uint8_t* out = e->wout[w].data();
             static const bool trace = getenv("HL_AMD_TRACE_WRITERS") != nullptr;
             const auto tk = std::chrono::steady_clock::now();
-            const size_t nb = write_slice(sp, ss, e->h_brec + (size_t)e->nmb * k, e->wscratch[w].data(), out, e->wout[w].size(),
+            // the slice header's disable_deblocking_filter_idc is the picture's own (slice.c:1739)
+            const StreamParams spk{e->W, e->H, e->p.qp, e->run_plan[k].deblock};
+            const size_t nb = write_slice(spk, ss, e->h_brec + (size_t)e->nmb * k, e->wscratch[w].data(), out, e->wout[w].size(),
                                           &e->run_bits[k], abort ? &gate : nullptr);
             if (!nb && abort && abort->load()) return;
             if (trace)
@@ -1543,8 +1574,13 @@ static std::vector<size_t> write_run(hl_amd_encoder_t* e, int m, int base, const
 // makes that exact inside a run), every stream when a bounded wait gave up.
 // Under rate control S and m are 1 and the picture's QP comes from the rate
 // controller.
+// C[s]: the m pictures' ctl of stream s (hl_amd_frame_ctl_t), or null.  Every
+// picture of the run carries its own type and settings -- FrameArgs, the
+// deblocking of its tasks, its slice header -- so a forced IDR or a changed
+// setting stays inside the launch.
 static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uint8_t* const* const* Y, const uint8_t* const* const* U,
-                            const uint8_t* const* const* V, hl_amd_result_t* const* res, int base)
+                            const uint8_t* const* const* V, hl_amd_result_t* const* res, int base,
+                            const hl_amd_frame_ctl_t* const* C = nullptr)
 {
     hl_amd_encoder_t* e0 = es[0];
     const size_t pic = (size_t)e0->W * e0->H * 3 / 2, nmb = e0->nmb;
@@ -1556,21 +1592,21 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
         hl_amd_encoder_t* e = es[si];
         if (e->rc && (m != 1 || S != 1)) return HL_AMD_ERROR_INVALID_STATE;
         HL_HIP_CHECK(ensure_batch(e, m));
-        // picture types, idr_pic_id and QP of the run, as m encode_frame calls would set them
-        e->run_intra.resize(m);
+        // picture types, settings, idr_pic_id and QP of the run, as m encode_frame calls would set them
+        // (on copies: the encoder's own move when the run commits)
         e->run_idr_id.resize(m);
+        e->run_plan.resize(m);
         e->run_qp.assign(m, e->p.qp);
         e->run_bits.assign(m, SliceBits{});
+        hl_amd_params_t live = e->p;
         for (int k = 0, gl = e->gop_left, idr = e->idr_pic_id; k < m; ++k) {
-            const bool intra = gl <= 0;
-            if (intra) gl = e->p.gop_size;
-            e->run_intra[k] = intra;
+            e->run_plan[k] = plan_picture(live, gl, C && C[si] ? C[si] + k : nullptr);
             e->run_idr_id[k] = idr;
-            idr += intra;
+            idr += e->run_plan[k].intra;
             --gl;
         }
         // rate control picks the picture's QP before it is coded (hl_codec_264.c:719-742)
-        if (e->rc) e->run_qp[0] = e->rc->begin_picture(e->run_intra[0] != 0);
+        if (e->rc) e->run_qp[0] = e->rc->begin_picture(e->run_plan[0].intra != 0);
         e->run_fallback = false;
         e->run_aborted.store(false, std::memory_order_release);
         if (e->timing) HL_HIP_CHECK(hipEventRecord(e->ev[0], e->stream));
@@ -1600,7 +1636,7 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
             PipeFrame& pf = e0->h_pf[slot];
             pf = PipeFrame{};
             FrameArgs& F = pf.F;
-            F = frame_args(e, e->run_intra[k] != 0, e->run_qp[k]);
+            F = frame_args(e, e->run_plan[k], e->run_qp[k]);
             uint8_t* cur = e->d_bpic + pic * k;
             F.src[0] = Y[si][k];
             F.src[1] = U[si][k];
@@ -1634,7 +1670,7 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
             F.run_chain = e->d_bchain;
             F.run_pos = k;
             F.carry_in = e->chain_end;
-            if (e0->helpers && !e->run_intra[k]) {
+            if (e0->helpers && !e->run_plan[k].intra) {
                 F.ispec = e->d_ispec;
                 F.hstate = e0->d_hstate + nmb * slot;
                 if (fam3) {
@@ -1653,7 +1689,7 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
             for (int c = 0; c < 3; ++c) pf.D.pic[c] = F.cur[c];
             pf.D.st = e->d_st;
             pf.pl_out = e->d_bpl + 4 * e->plsz * k;
-            pf.deblock = e->p.deblock;
+            pf.deblock = e->run_plan[k].deblock;
             pf.progress = d_progress;
             pf.rows = d_progress + kRowsAt + k;
             __atomic_store_n(e->h_progress + kRowsAt + k, 0, __ATOMIC_RELAXED);
@@ -1829,7 +1865,8 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
             for (int k = 0; k < m; ++k) {
                 hl_amd_result_t rr;
                 // under rate control the run's picture already has its QP (m == 1)
-                const int32_t rc = encode_frame(e, Y[si][k], U[si][k], V[si][k], &rr, e->rc ? e->run_qp[k] : -1);
+                const int32_t rc = encode_frame(e, Y[si][k], U[si][k], V[si][k], &rr, e->rc ? e->run_qp[k] : -1,
+                                                C && C[si] ? C[si] + k : nullptr);
                 if (rc) return rc;
                 store_result(e, base + k, rr, &res[si][k]);
                 // keep every picture's records and reconstruction in the run
@@ -1863,7 +1900,7 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
             o.hdr = e->hdr.data();
             o.hdr_size = e->hdr.size();
             if (e->frame_index == 0) o.type |= HL_AMD_RESULT_TYPE_HDR;
-            if (e->run_intra[k]) e->gop_left = e->p.gop_size;  // encode_frame's bookkeeping, picture by picture
+            (void)plan_picture(e->p, e->gop_left, C && C[si] ? C[si] + k : nullptr);  // encode_frame's bookkeeping, picture by picture
             if (e->rc) {  // hl_codec_264_rc_end_frame / _end_gop, hl_codec_264.c:1018-1031
                 RcPictureStats st{};
                 const MbRecord* rr = e->h_brec + nmb * k;
@@ -1871,11 +1908,11 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
                 st.header_bits = e->run_bits[k].header_bits;
                 st.texture_bits = e->run_bits[k].texture_bits;
                 st.nbits = (int32_t)((wsize[si][k] - 3) * 8);
-                e->rc->end_picture(e->run_intra[k] != 0, st, e->gop_left - 1 <= 0);
+                e->rc->end_picture(e->run_plan[k].intra != 0, st, e->gop_left - 1 <= 0);
             }
             e->last_qp = e->run_qp[k];
             ++e->pict_count;
-            if (e->run_intra[k]) ++e->idr_pic_id;
+            if (e->run_plan[k].intra) ++e->idr_pic_id;
             --e->gop_left;
             ++e->frame_index;
         }
@@ -1894,9 +1931,27 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
 }
 
 static int32_t encode_run(hl_amd_encoder_t* e, int m, const uint8_t* const* Y, const uint8_t* const* U, const uint8_t* const* V,
-                          hl_amd_result_t* res, int base)
+                          hl_amd_result_t* res, int base, const hl_amd_frame_ctl_t* ctl = nullptr)
 {
-    return encode_group(&e, 1, m, &Y, &U, &V, &res, base);
+    return encode_group(&e, 1, m, &Y, &U, &V, &res, base, &ctl);
+}
+
+// A call's ctl before anything is coded or queued (include/hartallo_amd.h):
+// what has no reference behaviour to match is refused.
+static int32_t check_ctl(const hl_amd_encoder_t* e, const hl_amd_frame_ctl_t* c, int n)
+{
+    for (int i = 0; c && i < n; ++i)
+        if (c[i].encoding != HL_AMD_ENCODING_AUTO && c[i].encoding != HL_AMD_ENCODING_INTRA && c[i].encoding != HL_AMD_ENCODING_INTER)
+            return HL_AMD_ERROR_NOT_IMPLEMENTED;  // RAW, LOSSLESS, unknown
+    for (int i = 0; c && i < n; ++i) {
+        // layers: forced types and changed settings are not implemented
+        if (e->svc && (c[i].encoding == HL_AMD_ENCODING_INTRA || c[i].me_range != e->p.me_range || c[i].deblock != e->p.deblock ||
+                       c[i].me_early_term != e->p.me_early_term || c[i].gop_size != e->p.gop_size))
+            return HL_AMD_ERROR_NOT_IMPLEMENTED;
+        // early termination reads the source one sample around the MB quadrants (rdo.c:895-896), as at create
+        if (c[i].me_early_term && (e->W < 32 || e->H < 32)) return HL_AMD_ERROR_INVALID_PARAMETER;
+    }
+    return HL_AMD_SUCCESS;
 }
 
 static void begin_call(hl_amd_encoder_t* e, int n)
@@ -1916,13 +1971,13 @@ static void begin_call(hl_amd_encoder_t* e, int n)
 // rate control every run is one picture (its QP needs the previous
 // picture's bits).  Results are those of n per-picture calls.
 static int32_t encode_pictures(hl_amd_encoder_t* e, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
-                               hl_amd_result_t* results)
+                               hl_amd_result_t* results, const hl_amd_frame_ctl_t* ctl = nullptr)
 {
     if (e->broken) return HL_AMD_ERROR_INVALID_STATE;
     begin_call(e, n);
     for (int i = 0; i < n;) {
         const int m = e->rc ? 1 : std::min(n - i, kMaxRun);
-        const int32_t rc = encode_run(e, m, y + i, u + i, v + i, results + i, i);
+        const int32_t rc = encode_run(e, m, y + i, u + i, v + i, results + i, i, ctl ? ctl + i : nullptr);
         if (rc) return rc;
         i += m;
     }
@@ -1931,6 +1986,13 @@ static int32_t encode_pictures(hl_amd_encoder_t* e, int n, const uint8_t* const*
 
 extern "C" int32_t hl_amd_encode_streams(hl_amd_encoder_t* const* encoders, int32_t count, int32_t n, const uint8_t* const* y,
                                          const uint8_t* const* u, const uint8_t* const* v, hl_amd_result_t* results)
+{
+    return hl_amd_encode_streams_ex(encoders, count, n, y, u, v, nullptr, results);
+}
+
+extern "C" int32_t hl_amd_encode_streams_ex(hl_amd_encoder_t* const* encoders, int32_t count, int32_t n, const uint8_t* const* y,
+                                            const uint8_t* const* u, const uint8_t* const* v, const hl_amd_frame_ctl_t* ctl,
+                                            hl_amd_result_t* results)
 {
     if (!encoders || count <= 0 || count > kMaxStreams || n <= 0 || !y || !u || !v || !results) return HL_AMD_ERROR_INVALID_PARAMETER;
     for (int i = 0; i < count * n; ++i)
@@ -1943,9 +2005,14 @@ extern "C" int32_t hl_amd_encode_streams(hl_amd_encoder_t* const* encoders, int3
         if (e->W != encoders[0]->W || e->H != encoders[0]->H || e->p.device != encoders[0]->p.device) return HL_AMD_ERROR_INVALID_FORMAT;
         if (e->rc || e->svc || e->broken) return HL_AMD_ERROR_INVALID_STATE;
     }
+    for (int s = 0; s < count && ctl; ++s) {
+        const int32_t rc = check_ctl(encoders[s], ctl + (size_t)s * n, n);
+        if (rc) return rc;
+    }
     for (int s = 0; s < count; ++s) begin_call(encoders[s], n);
     std::vector<const uint8_t* const*> Y(count), U(count), V(count);
     std::vector<hl_amd_result_t*> R(count);
+    std::vector<const hl_amd_frame_ctl_t*> C(count, nullptr);
     for (int i = 0; i < n;) {
         const int m = std::min(n - i, kMaxRun);
         for (int s = 0; s < count; ++s) {
@@ -1953,8 +2020,9 @@ extern "C" int32_t hl_amd_encode_streams(hl_amd_encoder_t* const* encoders, int3
             U[s] = u + (size_t)s * n + i;
             V[s] = v + (size_t)s * n + i;
             R[s] = results + (size_t)s * n + i;
+            if (ctl) C[s] = ctl + (size_t)s * n + i;
         }
-        const int32_t rc = encode_group(encoders, count, m, Y.data(), U.data(), V.data(), R.data(), i);
+        const int32_t rc = encode_group(encoders, count, m, Y.data(), U.data(), V.data(), R.data(), i, C.data());
         if (rc) return rc;
         i += m;
     }
@@ -1999,11 +2067,19 @@ extern "C" int32_t hl_amd_set_intra_helpers(hl_amd_encoder_t* e, int32_t enable)
 extern "C" int32_t hl_amd_encode_batch(hl_amd_encoder_t* e, int32_t n, const uint8_t* const* y, const uint8_t* const* u,
                                        const uint8_t* const* v, hl_amd_result_t* results)
 {
+    return hl_amd_encode_batch_ex(e, n, y, u, v, nullptr, results);
+}
+
+extern "C" int32_t hl_amd_encode_batch_ex(hl_amd_encoder_t* e, int32_t n, const uint8_t* const* y, const uint8_t* const* u,
+                                          const uint8_t* const* v, const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* results)
+{
     if (!e || n <= 0 || !y || !u || !v || !results) return HL_AMD_ERROR_INVALID_PARAMETER;
     for (int i = 0; i < n; ++i)
         if (!y[i] || !u[i] || !v[i]) return HL_AMD_ERROR_INVALID_PARAMETER;
     if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;  // frames still queued by the look-ahead come first (hl_amd_flush)
-    return encode_pictures(e, n, y, u, v, results);
+    const int32_t rc = check_ctl(e, ctl, n);
+    if (rc) return rc;
+    return encode_pictures(e, n, y, u, v, results, ctl);
 }
 
 extern "C" int32_t hl_amd_set_max_ref_frame(hl_amd_encoder_t* e, int32_t max_ref_frame)
@@ -2062,9 +2138,17 @@ extern "C" int32_t hl_amd_pipeline_occupancy(void)
 // next reference's quarter-pel planes fused into the tasks.
 extern "C" int32_t hl_amd_encode_device(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t* u, const uint8_t* v, hl_amd_result_t* r)
 {
+    return hl_amd_encode_device_ex(e, y, u, v, nullptr, r);
+}
+
+extern "C" int32_t hl_amd_encode_device_ex(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t* u, const uint8_t* v,
+                                           const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* r)
+{
     if (!e || !y || !u || !v || !r) return HL_AMD_ERROR_INVALID_PARAMETER;
     if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;  // frames still queued by the look-ahead come first (hl_amd_flush)
-    return encode_pictures(e, 1, &y, &u, &v, r);
+    const int32_t rc = check_ctl(e, ctl, 1);
+    if (rc) return rc;
+    return encode_pictures(e, 1, &y, &u, &v, r, ctl);
 }
 
 // Look-ahead: the queued frames as one batch; every result copied out (a
@@ -2081,8 +2165,19 @@ static int32_t la_run(hl_amd_encoder_t* e)
         u[i] = y[i] + ny;
         v[i] = u[i] + nc;
     }
+    // a frame queued without a ctl: AUTO with the settings of that moment (the ctl before it, else the encoder's)
+    bool any = false;
+    hl_amd_frame_ctl_t cur{HL_AMD_ENCODING_AUTO, e->p.me_range, e->p.deblock, e->p.me_early_term, e->p.gop_size};
+    for (int i = 0; i < n; ++i) {
+        if (e->la_has_ctl[i]) {
+            any = true;
+            cur = e->la_ctl[i];
+        }
+        else e->la_ctl[i] = cur;
+        cur.encoding = HL_AMD_ENCODING_AUTO;
+    }
     std::vector<hl_amd_result_t> res(n);
-    const int32_t rc = encode_pictures(e, n, y.data(), u.data(), v.data(), res.data());
+    const int32_t rc = encode_pictures(e, n, y.data(), u.data(), v.data(), res.data(), any ? e->la_ctl.data() : nullptr);
     if (rc) return rc;
     if (e->la_head == e->la_out.size()) {
         e->la_out.clear();
@@ -2136,10 +2231,24 @@ extern "C" int32_t hl_amd_flush(hl_amd_encoder_t* e, hl_amd_result_t* r)
 
 extern "C" int32_t hl_amd_encode(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t* u, const uint8_t* v, hl_amd_result_t* r)
 {
+    return hl_amd_encode_ex(e, y, u, v, nullptr, r);
+}
+
+extern "C" int32_t hl_amd_encode_ex(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t* u, const uint8_t* v,
+                                    const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* r)
+{
     if (!e || !y || !u || !v || !r) return HL_AMD_ERROR_INVALID_PARAMETER;
+    {
+        const int32_t rc = check_ctl(e, ctl, 1);
+        if (rc) return rc;
+    }
     if (e->lookahead > 1) {  // queue the frame (copied: the caller may reuse its buffer), code a full queue
         const size_t ny = (size_t)e->W * e->H, nc = (size_t)e->Wc * e->Hc, fb = ny + 2 * nc;
         if (!e->d_la) HL_HIP_CHECK(hipMalloc(&e->d_la, fb * e->lookahead));
+        e->la_ctl.resize(e->lookahead);
+        e->la_has_ctl.resize(e->lookahead);
+        e->la_has_ctl[e->la_n] = ctl != nullptr;
+        if (ctl) e->la_ctl[e->la_n] = *ctl;
         uint8_t* d = e->d_la + fb * e->la_n;
         HL_HIP_CHECK(hipMemcpyAsync(d, y, ny, hipMemcpyHostToDevice, e->stream));
         HL_HIP_CHECK(hipMemcpyAsync(d + ny, u, nc, hipMemcpyHostToDevice, e->stream));
@@ -2156,7 +2265,7 @@ extern "C" int32_t hl_amd_encode(hl_amd_encoder_t* e, const uint8_t* y, const ui
     HL_HIP_CHECK(hipMemcpyAsync(e->d_in[1], u, (size_t)e->Wc * e->Hc, hipMemcpyHostToDevice, e->stream));
     HL_HIP_CHECK(hipMemcpyAsync(e->d_in[2], v, (size_t)e->Wc * e->Hc, hipMemcpyHostToDevice, e->stream));
     const uint8_t *dy = e->d_in[0], *du = e->d_in[1], *dv = e->d_in[2];
-    return encode_pictures(e, 1, &dy, &du, &dv, r);
+    return encode_pictures(e, 1, &dy, &du, &dv, r, ctl);
 }
 
 extern "C" int32_t hl_amd_get_recon(hl_amd_encoder_t* e, uint8_t* y, uint8_t* u, uint8_t* v)

@@ -22,7 +22,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import Encoder, HlAmdError
+from ._lib import Encoder, FrameCtl, HlAmdError
 
 # HL_ERROR_T (hl_types.h:101-122)
 HL_ERROR_SUCCESS = 0
@@ -37,6 +37,12 @@ HL_CODEC_RESULT_TYPE_NONE = 0
 HL_CODEC_RESULT_TYPE_DATA = 1
 HL_CODEC_RESULT_TYPE_HDR = 2
 HL_VIDEO_CHROMA_YUV420 = 0
+# HL_VIDEO_ENCODING_TYPE_T (hl_types.h:262-274)
+HL_VIDEO_ENCODING_TYPE_AUTO = 0
+HL_VIDEO_ENCODING_TYPE_INTRA = 1
+HL_VIDEO_ENCODING_TYPE_INTER = 2
+HL_VIDEO_ENCODING_TYPE_LOSSLESS = 3
+HL_VIDEO_ENCODING_TYPE_RAW = 4
 
 
 @dataclass
@@ -87,6 +93,7 @@ class hl_frame_video_t:  # noqa: N801
     height: int = 0
     chroma: int = HL_VIDEO_CHROMA_YUV420
     data_ptr: tuple = ()
+    encoding: int = HL_VIDEO_ENCODING_TYPE_AUTO  # "could be changed at any time" (hl_frame.h:38-39)
 
 
 @dataclass
@@ -142,8 +149,13 @@ def hl_codec_encode(codec: hl_codec_t, frame: hl_frame_video_t, result: hl_codec
         except HlAmdError as e:
             return e.code
         codec.width, codec.height = frame.width, frame.height
+    # what the reference reads on every call: the frame's encoding type
+    # (hl_codec_264.c:705-718) and the settings it never snapshots (rdo.c:847,
+    # rdo.c:889, slice.c:1739, slice.c:1897, hl_codec_264.c:709-717); a changed
+    # codec.qp is ignored as the reference ignores it (hl_codec_264.c:465)
+    ctl = FrameCtl(frame.encoding, codec.me_range, codec.deblock_flag, codec.me_early_term_flag, codec.gop_size)
     try:
-        r = codec._enc.encode(*frame.data_ptr)
+        r = codec._enc.encode(*frame.data_ptr, ctl=ctl)
     except HlAmdError as e:
         return e.code
     result.type = r.type

@@ -144,6 +144,69 @@ int32_t hl_amd_encode_batch(hl_amd_encoder_t* encoder, int32_t n, const uint8_t*
 int32_t hl_amd_encode_streams(hl_amd_encoder_t* const* encoders, int32_t count, int32_t n, const uint8_t* const* y,
                               const uint8_t* const* u, const uint8_t* const* v, hl_amd_result_t* results);
 
+/* ---- per-frame encoding type and live settings ----
+ * What the reference reads on every hl_codec_encode call beside the planes:
+ * hl_frame_t.encoding (hl_frame.h:38-39, HL_VIDEO_ENCODING_TYPE_T,
+ * hl_types.h:262-274) and the hl_codec_t fields it never snapshots.  The
+ * hl_amd_*_ex calls take them per frame; a NULL ctl is the call without _ex
+ * (AUTO, settings as they are).
+ *   - picture type (hl_codec_264.c:705-718): a GOP counter that has run out
+ *     gives an IDR whatever is asked and reloads from gop_size; else AUTO and
+ *     INTER give a P picture and INTRA gives an IDR and reloads the counter
+ *     from gop_size.  frame_num goes on counting (encode.c:251), idr_pic_id
+ *     counts every IDR (encode.c:527-530), SPS / PPS are not sent again;
+ *   - me_range (rdo.c:847), deblock (slice.c:1897, the slice header's
+ *     disable_deblocking_filter_idc, slice.c:1739) and me_early_term
+ *     (rdo.c:889) apply from the call that carries them and stay until the
+ *     next _ex call changes them; gop_size likewise, and is read only where
+ *     the counter reloads (hl_codec_264.c:709, 717);
+ *   - qp is not here: the reference captures it at the first frame
+ *     (hl_codec_264.c:465) and ignores later changes;
+ *   - under rate control a forced IDR starts a GOP of the model as a
+ *     scheduled one does (hl_codec_264.c:723-737);
+ *   - RAW (I_PCM, whose reference output is truncated: hl_codec_264_mb.c:
+ *     247-310 overruns its bit buffer), LOSSLESS (no case in encode.c:230 and
+ *     slice.c:1819) and unknown values: HL_AMD_ERROR_NOT_IMPLEMENTED.
+ *     me_early_term on a picture under 32x32 (rdo.c:895-896):
+ *     HL_AMD_ERROR_INVALID_PARAMETER.  Every ctl of a call is checked before
+ *     anything is coded or queued, and a refused call leaves the encoder as
+ *     it was: the next call continues the stream;
+ *   - an encoder with layers (hl_amd_add_layer) accepts a ctl only with AUTO
+ *     or INTER and the settings it was created with, else
+ *     HL_AMD_ERROR_NOT_IMPLEMENTED;
+ *   - look-ahead: every queued frame keeps its ctl; the bytes are those of k
+ *     separate hl_amd_encode_ex calls.
+ * In hl_amd_encode_batch_ex / hl_amd_encode_streams_ex a forced IDR or a
+ * changed setting stays inside the frame-pipelined run: every picture of a
+ * run carries its own type and settings. */
+enum {
+    HL_AMD_ENCODING_AUTO = 0,
+    HL_AMD_ENCODING_INTRA,
+    HL_AMD_ENCODING_INTER,
+    HL_AMD_ENCODING_LOSSLESS,
+    HL_AMD_ENCODING_RAW
+}; /* = HL_VIDEO_ENCODING_TYPE_T */
+
+typedef struct hl_amd_frame_ctl_s {
+    int32_t encoding;       /* HL_AMD_ENCODING_* (hl_frame_t.encoding) */
+    int32_t me_range;       /* the hl_codec_t values at the time of this frame's call */
+    int32_t deblock;
+    int32_t me_early_term;
+    int32_t gop_size;
+} hl_amd_frame_ctl_t;
+
+int32_t hl_amd_encode_ex(hl_amd_encoder_t* encoder, const uint8_t* y, const uint8_t* u, const uint8_t* v,
+                         const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* result);
+int32_t hl_amd_encode_device_ex(hl_amd_encoder_t* encoder, const uint8_t* y, const uint8_t* u, const uint8_t* v,
+                                const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* result);
+/* ctl: n entries, frame by frame */
+int32_t hl_amd_encode_batch_ex(hl_amd_encoder_t* encoder, int32_t n, const uint8_t* const* y, const uint8_t* const* u,
+                               const uint8_t* const* v, const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* results);
+/* ctl: count * n entries, ctl[s * n + i] = frame i of stream s */
+int32_t hl_amd_encode_streams_ex(hl_amd_encoder_t* const* encoders, int32_t count, int32_t n, const uint8_t* const* y,
+                                 const uint8_t* const* u, const uint8_t* const* v, const hl_amd_frame_ctl_t* ctl,
+                                 hl_amd_result_t* results);
+
 /* rate control (hl_codec_t.rc_bitrate > 0; hl_codec_264.c:719-742, 1018-1031,
  * model hl_codec_264_rc.c): bitrate in bits/s, frame rate fps_den / fps_num
  * (hl_codec_t.fps, integer quotient), rc_basicunit (<= 0: the picture),

@@ -34,6 +34,7 @@ typedef struct hl_codec_264_gfx950_s {
     hl_size_t width, height; /* the encoder's (base layer's) size */
     hl_size_t layers;        /* spatial layers the encoder was opened with (0: AVC) */
     int input_type;          /* GFX950_* */
+    int32_t open_me_range, open_deblock, open_early_term, open_gop_size; /* the settings the encoder was opened with */
     hl_codec_t* dec;         /* stock H.264 codec that decodes for this object (created on the first decode) */
 } hl_codec_264_gfx950_t;
 
@@ -103,6 +104,10 @@ static HL_ERROR_T gfx950_open(hl_codec_264_gfx950_t* self, hl_codec_t* base, hl_
         return (HL_ERROR_T)err;
     self->width = W;
     self->height = H;
+    self->open_me_range = p.me_range;
+    self->open_deblock = p.deblock;
+    self->open_early_term = p.me_early_term;
+    self->open_gop_size = p.gop_size;
     return HL_ERROR_SUCCESS;
 }
 
@@ -134,10 +139,19 @@ static HL_ERROR_T gfx950_encode(hl_codec_t* base, const hl_frame_t* frame, hl_co
     hl_codec_264_gfx950_t* self = (hl_codec_264_gfx950_t*)base;
     const hl_frame_video_t* f = (const hl_frame_video_t*)frame;
     hl_amd_result_t r;
+    hl_amd_frame_ctl_t ctl;
     int32_t err;
     hl_size_t l, L;
     if (!self || !f || !result) return HL_ERROR_INVALID_PARAMETER;
     if (self->input_type == GFX950_DECODING) return HL_ERROR_INVALID_OPERATION; /* hl_codec_264.c:447-452 */
+    if (f->encoding == HL_VIDEO_ENCODING_TYPE_RAW || f->encoding == HL_VIDEO_ENCODING_TYPE_LOSSLESS) {
+        /* the stock plugin's I_PCM pictures overrun its bit buffer and come out truncated
+         * (hl_codec_264_mb.c:247-310), and LOSSLESS has no case in its switches (encode.c:230,
+         * slice.c:1819): no behaviour to match, refused rather than a different stream */
+        fprintf(stderr, "hl_codec_264_gfx950: hl_frame_t.encoding %s is not implemented\n",
+                f->encoding == HL_VIDEO_ENCODING_TYPE_RAW ? "HL_VIDEO_ENCODING_TYPE_RAW" : "HL_VIDEO_ENCODING_TYPE_LOSSLESS");
+        return HL_ERROR_NOT_IMPLEMENTED;
+    }
     if (base->threads_count > 1) {
         /* the stock plugin cuts every picture into threads_count slices
          * (hl_codec_264.c:571, encode.c:488-495); hl_codec_create defaults
@@ -164,6 +178,16 @@ static HL_ERROR_T gfx950_encode(hl_codec_t* base, const hl_frame_t* frame, hl_co
                     return (HL_ERROR_T)err;
             self->layers = L;
         }
+        /* layers: a forced keyframe or a setting changed since the open is not
+         * implemented; refused before any layer is coded */
+        if (f->encoding == HL_VIDEO_ENCODING_TYPE_INTRA || base->me_range != self->open_me_range ||
+            base->deblock_flag != self->open_deblock || base->me_early_term_flag != self->open_early_term ||
+            base->gop_size != self->open_gop_size) {
+            fprintf(stderr, "hl_codec_264_gfx950: spatial SVC with %s is not implemented\n",
+                    f->encoding == HL_VIDEO_ENCODING_TYPE_INTRA ? "a forced HL_VIDEO_ENCODING_TYPE_INTRA"
+                                                                    : "me_range / deblock_flag / me_early_term_flag / gop_size changed mid-stream");
+            return HL_ERROR_NOT_IMPLEMENTED;
+        }
         if ((err = hl_amd_encode_layer(self->enc, (int32_t)f->data_width[0], (int32_t)f->data_height[0], f->data_ptr[0],
                                        f->data_ptr[1], f->data_ptr[2], 0, &r)))
             return (HL_ERROR_T)err;
@@ -171,7 +195,17 @@ static HL_ERROR_T gfx950_encode(hl_codec_t* base, const hl_frame_t* frame, hl_co
     else {
         if (!self->enc || self->layers || f->data_width[0] != self->width || f->data_height[0] != self->height)
             if ((err = gfx950_open(self, base, f->data_width[0], f->data_height[0]))) return (HL_ERROR_T)err;
-        if ((err = hl_amd_encode(self->enc, f->data_ptr[0], f->data_ptr[1], f->data_ptr[2], &r)))
+        /* what the stock plugin reads on every call: the frame's encoding type
+         * (hl_codec_264.c:705-718) and the settings it never snapshots (rdo.c:847,
+         * rdo.c:889, slice.c:1739, slice.c:1897, hl_codec_264.c:709-717).  A changed
+         * base->qp is ignored, as the stock plugin ignores it: it captures the
+         * QP at the first frame (hl_codec_264.c:465). */
+        ctl.encoding = (int32_t)f->encoding; /* HL_AMD_ENCODING_* = HL_VIDEO_ENCODING_TYPE_T */
+        ctl.me_range = base->me_range;
+        ctl.deblock = base->deblock_flag;
+        ctl.me_early_term = base->me_early_term_flag;
+        ctl.gop_size = base->gop_size;
+        if ((err = hl_amd_encode_ex(self->enc, f->data_ptr[0], f->data_ptr[1], f->data_ptr[2], &ctl, &r)))
             return (HL_ERROR_T)err;
     }
     gfx950_result(base, &r, result);
