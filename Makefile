@@ -2,6 +2,7 @@
 #   hartallo_amd/libhartallo_amd.so  the product: HIP kernels + host writer + C ABI
 #   tests/emu/libhl_emu.so           test-only host build of the kernel logic
 #   tests/gpu_unit/libhl_unit.so     test-only GPU unit kernels (coop pipeline vs scalar primitives)
+#   tests/gpu_unit/libhl_unit_cand.so  test-only GPU unit kernel (the search's candidate slot)
 #   oracle/...                       test-only CPU oracle and reference build (oracle/Makefile)
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
@@ -23,20 +24,24 @@ all: product emu unit oracle sanitize
 
 product: hartallo_amd/libhartallo_amd.so
 emu: tests/emu/libhl_emu.so
-unit: tests/gpu_unit/libhl_unit.so
+unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so
 
 hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -shared -o $@ $(KSRC) $(HOSTSRC)
 
-# (hl_emu_ctl.hip = hl_emu_memo.hip plus emu_encode_frame_ex; hl_emu_memo.hip =
+# (hl_emu_search.hip = hl_emu_ctl.hip plus the search table's export;
+# hl_emu_ctl.hip = hl_emu_memo.hip plus emu_encode_frame_ex; hl_emu_memo.hip =
 # hl_emu.hip plus the memo's settings, counters and key export)
-EMUSRC := tests/emu/hl_emu_ctl.hip
-EMUINC := tests/emu/hl_emu_memo.hip tests/emu/hl_emu.hip
+EMUSRC := tests/emu/hl_emu_search.hip
+EMUINC := tests/emu/hl_emu_ctl.hip tests/emu/hl_emu_memo.hip tests/emu/hl_emu.hip
 tests/emu/libhl_emu.so: $(EMUSRC) $(EMUINC) $(HOSTSRC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -O2 -DHL_FAM3=1 -shared -o $@ $(EMUSRC) $(HOSTSRC)
 
 tests/gpu_unit/libhl_unit.so: tests/gpu_unit/hl_unit.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared -o $@ tests/gpu_unit/hl_unit.hip
+
+tests/gpu_unit/libhl_unit_cand.so: tests/gpu_unit/hl_unit_cand.hip $(HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared -o $@ tests/gpu_unit/hl_unit_cand.hip
 
 # sanitizer builds of the host code (tests/test_sanitizers.py, CPU):
 #   tests/sanitize/libhl_emu_asan.so  the emulator (the kernel logic on the
@@ -102,5 +107,5 @@ oracle: product  # oracle/_ref/drop_in_enc links the product library
 	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
-	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/gpu_unit/libhl_unit.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
+	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
 	$(MAKE) -C oracle clean

@@ -453,6 +453,7 @@ struct Ctx {
     LaneQ Q{};              // per-lane constants of the quad block pipeline (registers: the search loop reads them every pass)
 #endif
     int gx, gy;             // reference planes known complete for MBs (X <= gx, Y <= gy) (pipelined runs)
+    int rext = 0;           // how far past a partition a search's motion window reads (reach_wait; uniform, set at the MB start)
     int spec = 0;           // 1 = chain is still a row-start speculation (uniform)
     int par = 0;            // buffer parity of the last candidate step (Shared::cd, be_tcb)
     int p3 = 0;             // the last candidate step's slot of Shared::be_tcm (pass mod 3)
@@ -540,20 +541,14 @@ HD bool is8x8(int et) { return et == ET_P8x8 || et == ET_P8x8REF0; }
 
 // log2 of a power of two (partition sizes 4, 8, 16): divisions by a
 // runtime partition size compile to long VALU sequences; shifts do not
-HD int lg2(int v)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return 31 - __clz(v);
-#else
-    return 31 - __builtin_clz((unsigned)v);
-#endif
-}
+// (constexpr: the per-search table kSearchTab is derived from these at compile time)
+constexpr HD int lg2(int v) { return 31 - __builtin_clz((unsigned)v); }
 // origin of partition pi of a 16x16 MB split into pw x ph partitions
-HD int part_x(int pi, int pw) { return (pi & ((16 >> lg2(pw)) - 1)) << lg2(pw); }
-HD int part_y(int pi, int pw, int ph) { return (pi >> (4 - lg2(pw))) << lg2(ph); }
+constexpr HD int part_x(int pi, int pw) { return (pi & ((16 >> lg2(pw)) - 1)) << lg2(pw); }
+constexpr HD int part_y(int pi, int pw, int ph) { return (pi >> (4 - lg2(pw))) << lg2(ph); }
 // origin of sub-partition spi of an 8x8 partition split into sw x sh
-HD int sub_x(int spi, int sw) { return (spi & ((8 >> lg2(sw)) - 1)) << lg2(sw); }
-HD int sub_y(int spi, int sw, int sh) { return (spi >> (3 - lg2(sw))) << lg2(sh); }
+constexpr HD int sub_x(int spi, int sw) { return (spi & ((8 >> lg2(sw)) - 1)) << lg2(sw); }
+constexpr HD int sub_y(int spi, int sw, int sh) { return (spi >> (3 - lg2(sw))) << lg2(sh); }
 
 HD void sub_part_idx(const NbInfo& n, int xW, int yW, int& pi, int& spi)  // mb.h:313-339
 {
@@ -584,18 +579,43 @@ HD MvN mv_at(const Shared& S, int bx, int by)
     return n;
 }
 
-// A, B, C (C replaced by D when not available) of the (sub)partition at
-// luma (x, y) of width ppw; all four cells are read in one batch
-HD void nb_motion(const Shared& S, int x, int y, int ppw, MvN nb[3])
+// The motion-grid cells (index (by + 1) * 6 + bx + 1 into S.mvg / S.mvs) of
+// the neighbours A, B, C, D of the (sub)partition at luma (x, y) of width
+// ppw, and whether C lies where the grid can hold it (else C is D's cell):
+// pure geometry, so the per-search table holds it (kSearchTab)
+struct NbCells {
+    int a, b, c, d, c_in;
+};
+constexpr HD NbCells nb_cells(int x, int y, int ppw)
 {
     const int bx = x >> 2, by = y >> 2;
     const int cx = (x + ppw) >> 2;
     const bool c_in = cx <= 4 && !(cx == 4 && by > 0);
-    const MvN a = mv_at(S, bx - 1, by), b = mv_at(S, bx, by - 1), d = mv_at(S, bx - 1, by - 1);
-    const MvN cc = mv_at(S, c_in ? cx : bx - 1, by - 1);
+    return NbCells{(by + 1) * 6 + bx, by * 6 + bx + 1, by * 6 + (c_in ? cx : bx - 1) + 1, by * 6 + bx, c_in};
+}
+HD MvN mv_cell(const Shared& S, int cell)
+{
+    MvN n;
+    n.st = (&S.mvs[0][0])[cell];
+    const int v = (&S.mvg[0][0])[cell];
+    n.mv[0] = n.st == 2 ? (int)(int16_t)(v & 0xFFFF) : 0;
+    n.mv[1] = n.st == 2 ? (v >> 16) : 0;
+    return n;
+}
+// A, B, C (C replaced by D when not available) from their cells; all four
+// cells are read in one batch
+HD void nb_motion_cells(const Shared& S, int ca, int cb, int cc_, int cd, bool c_in, MvN nb[3])
+{
+    const MvN a = mv_cell(S, ca), b = mv_cell(S, cb), d = mv_cell(S, cd);
+    const MvN cc = mv_cell(S, cc_);
     nb[0] = a;
     nb[1] = b;
     nb[2] = (c_in && cc.st != 0) ? cc : d;
+}
+HD void nb_motion(const Shared& S, int x, int y, int ppw, MvN nb[3])
+{
+    const NbCells k = nb_cells(x, y, ppw);
+    nb_motion_cells(S, k.a, k.b, k.c, k.d, k.c_in != 0, nb);
 }
 
 HD int median3(int a, int b, int c)
@@ -605,32 +625,25 @@ HD int median3(int a, int b, int c)
     return a + b + c - mx - mn;
 }
 
-// shape of the partitioning being searched (registers, not LDS)
-struct PartShape {
-    int part_w, part_h, sub_w, sub_h, is8;
-};
-
-// 8.4.1.3 (utils.c:751-831) for partition (pi, spi) of partitioning ps
-HD void mvp(const Shared& S, const PartShape& ps, int pi, int spi, int out[2])
+// The directional predictor of 16x8 / 8x16 partitions (8.4.1.3): the
+// neighbour taken alone when it is inter-coded.  0 = none (median), 1 = B
+// (16x8 upper), 2 = A (16x8 lower, 8x16 left), 3 = C (8x16 right)
+constexpr HD int mvp_dir(int part_w, int part_h, int pi)
 {
-    const int x = part_x(pi, ps.part_w);
-    const int y = part_y(pi, ps.part_w, ps.part_h);
-    int xS = 0, yS = 0, ppw = ps.part_w;
-    if (ps.is8) {
-        xS = sub_x(spi, ps.sub_w);
-        yS = sub_y(spi, ps.sub_w, ps.sub_h);
-        ppw = ps.sub_w;
-    }
-    MvN nb[3];
-    nb_motion(S, x + xS, y + yS, ppw, nb);
+    return (part_w == 16 && part_h == 8) ? (pi == 0 ? 1 : 2) : ((part_w == 8 && part_h == 16) ? (pi == 0 ? 2 : 3) : 0);
+}
+
+// 8.4.1.3 (utils.c:751-831) from the neighbours A, B, C of nb_motion and the
+// partition's directional rule (mvp_dir)
+HD void mvp_of(const MvN nb[3], int dir, int out[2])
+{
 #if defined(__HIP_DEVICE_COMPILE__)
     {
         // 8.4.1.3 as selects (the values are uniform but live in VGPRs: every
         // branch on them would be an exec-mask branch)
         const MvN A = nb[0], B = nb[1], C = nb[2];
         const bool a2 = A.st == 2, b2 = B.st == 2, c2 = C.st == 2;
-        const bool p168 = ps.part_w == 16 && ps.part_h == 8, p816 = ps.part_w == 8 && ps.part_h == 16;
-        int sel = (p168 && pi == 0 && b2) ? 1 : ((p168 && pi == 1 && a2) ? 0 : ((p816 && pi == 0 && a2) ? 0 : ((p816 && pi == 1 && c2) ? 2 : -1)));
+        int sel = (dir == 1 && b2) ? 1 : ((dir == 2 && a2) ? 0 : ((dir == 3 && c2) ? 2 : -1));
         const bool rep = B.st == 0 && C.st == 0 && A.st != 0;  // B and C replaced by A
         const bool eb2 = rep ? a2 : b2, ec2 = rep ? a2 : c2;
         const int bx = rep ? A.mv[0] : B.mv[0], by = rep ? A.mv[1] : B.mv[1];
@@ -648,10 +661,9 @@ HD void mvp(const Shared& S, const PartShape& ps, int pi, int spi, int out[2])
     MvN A = nb[0], B = nb[1], C = nb[2];
     int rA = A.st == 2 ? 0 : -1, rB = B.st == 2 ? 0 : -1, rC = C.st == 2 ? 0 : -1;
     int sel = -1;
-    if (ps.part_w == 16 && ps.part_h == 8 && pi == 0 && rB == 0) sel = 1;
-    else if (ps.part_w == 16 && ps.part_h == 8 && pi == 1 && rA == 0) sel = 0;
-    else if (ps.part_w == 8 && ps.part_h == 16 && pi == 0 && rA == 0) sel = 0;
-    else if (ps.part_w == 8 && ps.part_h == 16 && pi == 1 && rC == 0) sel = 2;
+    if (dir == 1 && rB == 0) sel = 1;
+    else if (dir == 2 && rA == 0) sel = 0;
+    else if (dir == 3 && rC == 0) sel = 2;
     if (sel < 0) {
         if (B.st == 0 && C.st == 0 && A.st != 0) {
             B = A;
@@ -681,8 +693,91 @@ HD void skip_mv(const Shared& S, int out[2])
         out[0] = out[1] = 0;
         return;
     }
-    const PartShape p16{16, 16, 16, 16, 0};
-    mvp(S, p16, 0, 0, out);
+    mvp_of(nb, 0, out);  // (the 16x16 partition's predictor: the same neighbours, no directional rule)
+}
+
+// Per-search constants.  The 41 partition searches of a macroblock are fixed:
+// partitioning j (kParts[j]), partition pi, sub-partition spi.  What a search
+// needs of them -- its origin and shape (PartGeo), the candidate budget of a
+// pass, the raster index of a single-block partition, the four motion-grid
+// cells and the directional rule of its MV predictor -- is geometry alone:
+// one function (make_search_k) packs it into an 8-byte entry from the
+// functions that define it (part_x .. sub_y, nb_cells, mvp_dir, blk_idx), the
+// search reads every constant as a field of that entry, and kSearchTab is the
+// function evaluated at compile time for every search
+// (tests/test_search_table.py checks the 41 entries).
+// On the device a search computes its entry with the same function at run
+// time (scalar arithmetic on the uniform j, pi, spi): the 8-byte scalar load
+// of the entry (HL_SEARCH_TAB 1) puts a memory round trip at the head of
+// every search's chain and measured 0.7-1.0 % slower
+// (profiles/r08_ab_search_chain.log).  The host path reads the table.
+#ifndef HL_SEARCH_TAB
+#define HL_SEARCH_TAB 0
+#endif
+struct SearchK {
+    // px | py << 4 | log2(pw / 4) << 8 | log2(ph / 4) << 10 | budget << 12 | blk_idx(px, py) << 18 | mvp_dir << 22 |
+    // c_in << 24 | 1 << 25 (an entry of a search that exists)
+    uint32_t geo;
+    uint32_t nbc;  // motion-grid cells (nb_cells): A | B << 5 | C << 10 | D << 15
+};
+constexpr int kSearches = 41;
+constexpr HD int search_slot(int j, int pi, int spi) { return (j << 4) | (pi << 2) | spi; }  // (a padded table: no base lookup)
+constexpr HD SearchK make_search_k(int j, int pi, int spi)
+{
+    const PartDef pd = kParts[j];
+    int px = part_x(pi, pd.part_w), py = part_y(pi, pd.part_w, pd.part_h);
+    if (pd.num_part == 4) {
+        px += sub_x(spi, pd.sub_w);
+        py += sub_y(spi, pd.sub_w, pd.sub_h);
+    }
+    const int lbw = lg2(pd.sub_w >> 2), lbh = lg2(pd.sub_h >> 2), lnb = lbw + lbh;
+    // candidates a pass may hold: chains of speculative steps while they fit (0: one step per pass)
+    const int budget = (1 << lnb) <= kSpecMaxBlocks ? ((kPassItems >> lnb) < kMaxCand ? (kPassItems >> lnb) : kMaxCand) : 0;
+    const NbCells nc = nb_cells(px, py, pd.sub_w);  // (a partition's width is its sub-partition's: kParts)
+    const int dir = mvp_dir(pd.part_w, pd.part_h, pi);
+    return SearchK{(uint32_t)(px | (py << 4) | (lbw << 8) | (lbh << 10) | (budget << 12) | (blk_idx(px, py) << 18) | (dir << 22) |
+                              (nc.c_in << 24) | (1 << 25)),
+                   (uint32_t)(nc.a | (nc.b << 5) | (nc.c << 10) | (nc.d << 15))};
+}
+struct SearchTab {
+    SearchK e[7 * 16];
+};
+constexpr SearchTab make_search_tab()
+{
+    SearchTab t{};
+    for (int j = 0; j < 7; ++j)
+        for (int pi = 0; pi < kParts[j].num_part; ++pi)
+            for (int spi = 0; spi < kParts[j].num_sub; ++spi) t.e[search_slot(j, pi, spi)] = make_search_k(j, pi, spi);
+    return t;
+}
+static constexpr SearchTab kSearchTab = make_search_tab();
+constexpr int count_searches()
+{
+    int n = 0;
+    for (int i = 0; i < 7 * 16; ++i) n += (int)((kSearchTab.e[i].geo >> 25) & 1);
+    return n;
+}
+static_assert(count_searches() == kSearches, "one entry per (j, pi, spi)");
+static_assert(kMaxCand < 64, "SearchK::geo: budget in 6 bits");
+static_assert(kParts[0].sub_w == kParts[0].part_w && kParts[1].sub_w == kParts[1].part_w && kParts[2].sub_w == kParts[2].part_w,
+              "an unsplit partition's predictor width is its sub_w");
+// the MV predictor of a search from its entry: one batch of four cell reads
+HD void mvp(const Shared& S, const SearchK k, int out[2])
+{
+    MvN nb[3];
+    // The cells' indices are scalar, and left so the compiler reads the
+    // cells as uniform values: it then takes each result to a scalar
+    // register as it arrives, in three dependent LDS round trips (1.4 %
+    // of the frame rate).  An opaque zero in a vector
+    // register keeps the eight reads one batch and 8.4.1.3 the selects of
+    // mvp_of.
+    int z = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(z));
+#endif
+    nb_motion_cells(S, (int)(k.nbc & 31) + z, (int)((k.nbc >> 5) & 31) + z, (int)((k.nbc >> 10) & 31) + z, (int)((k.nbc >> 15) & 31) + z,
+                    (k.geo >> 24) & 1, nb);
+    mvp_of(nb, (int)((k.geo >> 22) & 3), out);
 }
 
 // marks the 4x4 blocks of the luma rectangle as decided with motion mv
@@ -1248,7 +1343,24 @@ HD void mb_begin(Ctx& c)
 // --------------------------------------------------------------------------
 struct PartGeo {
     int px, py, pw, ph, nbw, nblk, lbw, lnb;  // lbw / lnb = log2(nbw) / log2(nblk)
+    int bi;                                   // blk_idx(px, py): a single-block partition's block
 };
+// the search's shape from its table entry (field extracts of one word)
+HD PartGeo part_geo(const SearchK k)
+{
+    PartGeo g;
+    const int lbh = (int)((k.geo >> 10) & 3);
+    g.px = (int)(k.geo & 15);
+    g.py = (int)((k.geo >> 4) & 15);
+    g.lbw = (int)((k.geo >> 8) & 3);
+    g.lnb = g.lbw + lbh;
+    g.pw = 4 << g.lbw;
+    g.ph = 4 << lbh;
+    g.nbw = 1 << g.lbw;
+    g.nblk = 1 << g.lnb;
+    g.bi = (int)((k.geo >> 18) & 15);
+    return g;
+}
 
 // Quarter-pel phase table kQpelTab packed 9 bits per phase:
 // plane1 | dx1 << 2 | dy1 << 3 | has2 << 4 | plane2 << 5 | dx2 << 7 | dy2 << 8
@@ -1341,9 +1453,9 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
         const auto base = gmem(F.pl[0]);
         // single-block partitions: both nC neighbours lie outside the partition,
         // so nC is fixed for its whole search (read here, beside the loads)
-        const int nc1 = g.nblk == 1 ? nc_luma_of(S, blk_idx(g.px, g.py), [&](int ni) -> int { return S.tc[ni]; }) : 0;
+        const int nc1 = g.nblk == 1 ? nc_luma_of(S, g.bi, [&](int ni) -> int { return S.tc[ni]; }) : 0;
         if (HL_F3REC(c) && g.nblk == 1 && c.tid == 0)  // fam3_helper: its entry reads (lane 0; phase 2 does not run)
-            nc_luma_iv(S, blk_idx(g.px, g.py), [&](int ni, bool& e) -> int {
+            nc_luma_iv(S, g.bi, [&](int ni, bool& e) -> int {
                 e = !((S.f3w >> ni) & 1);
                 return S.tc[ni];
             }, S.f3lo, S.f3hi);
@@ -1365,7 +1477,7 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
                 R.bits[ci] = bits;
                 R.dist[ci] = dist;
                 R.single[ci] = tc ? sctr : 0;
-                R.cbp[ci] = tc ? 1 << blk_idx(g.px, g.py) : 0;
+                R.cbp[ci] = tc ? 1 << g.bi : 0;
                 R.last[ci] = tc ? sctr : -1;
             }
         };
@@ -1834,8 +1946,11 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
 // last_l: candidate (tid & 31)'s R.last when the caller has it in a register
 // (device; -2 = read it here)
 template <bool REC = false>
-HD void commit_candidates(Ctx& c, const PartGeo& g, int n, int last_l = -2)
+HD void commit_candidates(Ctx& c, const PartGeo& g, int n, int last_l = -1, bool by_lane = false)
 {
+    // by_lane (device): last_l is the lane's own value of CandRes::last for a
+    // candidate below n, else -1, the lanes in the candidates' order
+    // (search_partition holds a pass's results that way); otherwise read here
     Shared& S = c.S;
     const Shared::CandRes& R = S.cd[c.par];
     HL_PROF_T(tp2);
@@ -1853,12 +1968,13 @@ HD void commit_candidates(Ctx& c, const PartGeo& g, int n, int last_l = -2)
     }
     {  // last candidate that wrote the counter (vectorised over the pass)
         const int l = c.tid & 31;
-        const int v = l < n ? (last_l == -2 ? R.last[l] : last_l) : -1;
-        const unsigned long long bal = __ballot(v >= 0) & 0xFFFFFFFFull;
+        const int v = by_lane ? last_l : (l < n ? R.last[l] : -1);
+        const unsigned long long bal = __ballot(v >= 0) & (by_lane ? ~0ull : 0xFFFFFFFFull);
         if (bal) chain_write(c, __builtin_amdgcn_readlane(v, 63 - __clzll((long long)bal)));
     }
 #else
     (void)last_l;
+    (void)by_lane;
     for (int k = 0; k < g.nblk; ++k) {
         const int hx = k % g.nbw, hy = k / g.nbw;
         const int bi = blk_idx(g.px + (hx << 2), g.py + (hy << 2));
@@ -1910,8 +2026,6 @@ struct Best {
     int dist, single, cbp, mv[2];
 };
 
-HD int ilog2_small(int v) { return v >= 16 ? 4 : (v >= 8 ? 3 : (v >= 4 ? 2 : (v >= 2 ? 1 : 0))); }
-
 // Pipelined runs (hl_pipeline.h): the task of a picture after which the
 // quarter-pel planes of all its MBs (X' <= X, Y' <= Y) are final.  Plane
 // blocks of (X, Y) run in task (X+2, Y+2), in the last rows in (X+3, mbh-1)
@@ -1938,7 +2052,7 @@ HD void reach_wait(Ctx& c, const PartGeo& g, const int pmv[2])
 #if defined(__HIP_DEVICE_COMPILE__)
     const FrameArgs& F = c.F;
     if (!F.ref_done) return;
-    const int ext = F.me_range + (F.me_range >> 1) + ((F.me_range + 3) >> 2) + 2;
+    const int ext = c.rext;  // me_range + me_range / 2 + ceil(me_range / 4) + 2
     const int px = c.xL + g.px + g.pw - 1 + (pmv[0] > 0 ? pmv[0] >> 2 : 0) + ext;
     const int py = c.yL + g.py + g.ph - 1 + (pmv[1] > 0 ? pmv[1] >> 2 : 0) + ext;
     int X = min(F.mbw - 1, max(0, px >> 4)), Y = min(F.mbh - 1, max(0, py >> 4));
@@ -1967,26 +2081,20 @@ HD void reach_wait(Ctx& c, const PartGeo& g, const int pmv[2])
 // Diamond search of one (sub)partition, me_ds.c:104-477.  Returns true when
 // the P_Skip probe fired (16x16 only).
 template <bool REC = false>
-HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
+HD bool search_partition(Ctx& c, int j, int pi, int spi, bool probe)
 {
     // (no HL_FRESH_TID here: ROCm 7.2's greedy register allocator crashes on it)
     Shared& S = c.S;
     HL_PROF_T(tsp);
-    const int xP = part_x(pi, pd.part_w), yP = part_y(pi, pd.part_w, pd.part_h);
-    int xS = 0, yS = 0;
-    if (pd.num_part == 4) {
-        xS = sub_x(spi, pd.sub_w);
-        yS = sub_y(spi, pd.sub_w, pd.sub_h);
-    }
-    PartGeo g;
-    g.px = xP + xS;
-    g.py = yP + yS;
-    g.pw = pd.sub_w;
-    g.ph = pd.sub_h;
-    g.nbw = g.pw >> 2;
-    g.nblk = (g.pw >> 2) * (g.ph >> 2);
-    g.lbw = ilog2_small(g.nbw);
-    g.lnb = ilog2_small(g.nblk);
+    // the search's constants (SearchK): the table's entry on the host, the
+    // same function at run time on the device (j, pi and spi are uniform
+    // loop counters: scalar arithmetic; see HL_SEARCH_TAB)
+#if HL_SEARCH_TAB || !defined(__HIP_DEVICE_COMPILE__)
+    const SearchK sk = kSearchTab.e[search_slot(j, pi, spi)];
+#else
+    const SearchK sk = make_search_k(j, pi, spi);
+#endif
+    const PartGeo g = part_geo(sk);
     Best b;
     b.cost = 1.7976931348623157e308;
     b.dist = 0x7fffffff;
@@ -1997,8 +2105,7 @@ HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
     int pmv[2];
     {
         HL_PROF_T(tm);
-        const PartShape ps{pd.part_w, pd.part_h, pd.sub_w, pd.sub_h, pd.num_part == 4};
-        mvp(S, ps, pi, spi, pmv);
+        mvp(S, sk, pmv);
         pmv[0] = uni(pmv[0]);
         pmv[1] = uni(pmv[1]);
         HL_PROF_ADD(c, 4, tm);
@@ -2078,14 +2185,16 @@ HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
         return (int)((w >> (9 * k)) & 0x1FF);
     };
     const int range = c.F.me_range;
-    const int budget = g.nblk <= kSpecMaxBlocks ? min(kMaxCand, kPassItems >> g.lnb) : 0;  // 0: one step per pass
+    const int budget = (int)((sk.geo >> 12) & 63);  // candidates a pass may hold (0: one step per pass)
     const int nc0 = (pmv[0] != 0 || pmv[1] != 0) ? 2 : 1;
     int stage = 3, flags = 0x1FF, cx = 0, cy = 0, left = 0, right = 0, top = 0, bottom = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
-    // a pass's candidate results, lane l (and l + 32) holding candidate l:
-    // loaded once per pass, then every pick and take is register work
+    // a pass's candidate results, each lane holding the candidate it
+    // generated (pv_ci; kMaxCand: none): loaded once per pass, then every
+    // pick and take is register work (bi = the candidate's lane)
     double pv_cost = 0.0;
-    int pv_single = 0, pv_dist = 0, pv_cbp = 0, pv_mvx = 0, pv_mvy = 0, pv_pad = 0, pv_last = -1;
+    int pv_single = 0, pv_dist = 0, pv_cbp = 0, pv_mvx = 0, pv_mvy = 0, pv_pad = 0, pv_last = -1, pv_ci = kMaxCand;
+    unsigned long long gen = 0;  // the lanes whose point the pass evaluates (uniform)
     auto take = [&](int bi, double m) {
         b.cost = m;
         b.single = __builtin_amdgcn_readlane(pv_single, bi);
@@ -2094,23 +2203,6 @@ HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
         b.mv[0] = __builtin_amdgcn_readlane(pv_mvx, bi);
         b.mv[1] = __builtin_amdgcn_readlane(pv_mvy, bi);
         return __builtin_amdgcn_readlane(pv_pad, bi);
-    };
-    // the sequential strict-< scan of candidates [lo, hi) (me_ds.c:339-347):
-    // index of the first candidate with the smallest cost, and that cost
-    auto pick = [&](int lo, int hi, double& m) -> int {
-        const int l = c.tid & 31;
-        const bool in = l >= lo && l < hi;
-        const double v = in ? pv_cost : 1.7976931348623157e308;
-        const double rm = row_min_f64(v);
-        const unsigned long long b0 = __builtin_bit_cast(unsigned long long, rm);
-        const double m0 = __builtin_bit_cast(double, (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(b0 >> 32), 0) << 32 |
-                                                         (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b0, 0));
-        const double m1 = __builtin_bit_cast(double, (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(b0 >> 32), 16) << 32 |
-                                                         (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b0, 16));
-        const double mn = fmin(m0, m1);
-        const unsigned long long bal = __ballot(in && v == mn) & 0xFFFFFFFFull;
-        m = mn;
-        return __ffsll((long long)bal) - 1;
     };
 #else
     auto take = [&](int bi, double m) {
@@ -2170,7 +2262,8 @@ HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
                 lo[k] = __popcll(bal & ((1ull << (16 * k)) - 1ull));
                 n[k] = __popcll(bal & (0xFFFFull << (16 * k)));
             }
-            if (en) put_cand(c, g.px, g.py, g.pw, g.ph, __popcll(bal & ((1ull << i) - 1ull)), mx * (1 << sh), my * (1 << sh), i & 15, true);
+            if (en) put_cand(c, g.px, g.py, g.pw, g.ph, lanes_below(bal), mx * (1 << sh), my * (1 << sh), i & 15, true);
+            gen = bal;
         }
 #if defined(HL_STEP_PROF)
         HL_PROF_ADD(c, 19, tgen);  // the pass's candidates generated and stored
@@ -2212,45 +2305,44 @@ HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
         }
         HL_PROF_T(tsel);
 #if defined(__HIP_DEVICE_COMPILE__)
+        // The pass's results are loaded in the layout the candidates were
+        // generated in: lane 16 j + i of every wave holds point i of step j (its
+        // candidate is the number of enabled lanes below it, and candidates
+        // are numbered in lane order), so each step of the chain lies in a DPP
+        // row of its own.
+        const bool pv_en = (gen >> (c.tid & 63)) & 1;
         {
-            const int l = c.tid & 31;
+            const int ci = pv_en ? lanes_below(gen) : 0;
             const Shared::CandRes& R = S.cd[c.par];
-            const CandSlot cs = S.wc[c.tid >> 6][l];
-            pv_cost = R.cost[l];
-            pv_single = R.single[l];
-            pv_dist = R.dist[l];
-            pv_cbp = R.cbp[l];
-            pv_last = R.last[l];
+            const CandSlot cs = S.wc[c.tid >> 6][ci];
+            pv_cost = pv_en ? R.cost[ci] : 1.7976931348623157e308;
+            pv_single = R.single[ci];
+            pv_dist = R.dist[ci];
+            pv_cbp = R.cbp[ci];
+            pv_last = R.last[ci];
+            pv_ci = pv_en ? ci : kMaxCand;
             pv_mvx = cs.mvx;
             pv_mvy = cs.mvy;
             pv_pad = cs.pad & 15;
         }
         // The sequential strict-< scans of every step of the chain
-        // (me_ds.c:339-347) at once: four independent DPP minimum chains over
-        // the candidate lanes of each step, then each step's smallest cost and
-        // the first candidate holding it as uniform values.  Resolving the
-        // chain below is then scalar work.
+        // (me_ds.c:339-347) at once: one DPP row minimum serves the four
+        // steps, then each step's smallest cost and the first lane holding it
+        // (the lowest lane is the lowest candidate) as uniform values.
+        // Resolving the chain below is then scalar work.  A step the pass
+        // does not hold has no enabled lane: the largest double, lane -1.
         double sm[kMaxSeg];
         int sb[kMaxSeg];
         {
-            const int l = c.tid & 31;
-            bool in[kMaxSeg];
-            double v[kMaxSeg], rm[kMaxSeg];
+            const double rm = row_min_f64(pv_cost);
+            const unsigned long long b0 = __builtin_bit_cast(unsigned long long, rm);
+            const unsigned long long eq = __ballot(pv_en && pv_cost == rm);
 #pragma unroll
             for (int j = 0; j < kMaxSeg; ++j) {
-                in[j] = j < nseg && l >= lo[j] && l < lo[j] + n[j];
-                v[j] = in[j] ? pv_cost : 1.7976931348623157e308;
-                rm[j] = row_min_f64(v[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < kMaxSeg; ++j) {
-                const unsigned long long b0 = __builtin_bit_cast(unsigned long long, rm[j]);
-                const double m0 = __builtin_bit_cast(double, (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(b0 >> 32), 0) << 32 |
-                                                                 (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b0, 0));
-                const double m1 = __builtin_bit_cast(double, (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(b0 >> 32), 16) << 32 |
-                                                                 (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b0, 16));
-                sm[j] = fmin(m0, m1);
-                sb[j] = __ffsll((long long)(__ballot(in[j] && v[j] == sm[j]) & 0xFFFFFFFFull)) - 1;
+                sm[j] = __builtin_bit_cast(double, (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(b0 >> 32), 16 * j) << 32 |
+                                                       (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b0, 16 * j));
+                const unsigned e16 = (unsigned)(eq >> (16 * j)) & 0xFFFFu;
+                sb[j] = e16 ? 16 * j + __ffs((int)e16) - 1 : -1;
             }
         }
 #if defined(HL_STEP_PROF)
@@ -2337,7 +2429,7 @@ HD bool search_partition(Ctx& c, const PartDef& pd, int pi, int spi, bool probe)
 #if defined(HL_STEP_PROF)
         HL_PROF_ADD(c, 18, tres);  // the chain resolved
 #endif
-        if (used) commit_candidates<REC>(c, g, used, pv_last);
+        if (used) commit_candidates<REC>(c, g, used, pv_ci < used ? pv_last : -1, true);
 #else
         if (used) commit_candidates<REC>(c, g, used);
 #endif
@@ -4136,7 +4228,7 @@ HD bool search_family_part(Ctx& c, int j, int fam, double& cost_sum, int& single
     bool prob = false;
     for (int pi = 0; pi < pd.num_part; ++pi)
         for (int spi = 0; spi < pd.num_sub; ++spi) {
-            const bool p = search_partition<REC>(c, pd, pi, spi, j == 0 && pi == 0 && spi == 0);
+            const bool p = search_partition<REC>(c, j, pi, spi, j == 0 && pi == 0 && spi == 0);
             if (j == 0 && pi == 0 && spi == 0) prob = p;
         }
     for (int pi = 0; pi < pd.num_part; ++pi)
@@ -4917,6 +5009,7 @@ HD void encode_mb(const FrameArgs& F, Shared& S, int addr, int tid, int nthr, in
     Ctx c{F, S, tid, nthr, addr, addr % F.mbw, addr / F.mbw, (addr % F.mbw) * 16, (addr / F.mbw) * 16, s_in, 0, 0};
     c.gx = gx;
     c.gy = gy;
+    c.rext = uni(F.me_range + (F.me_range >> 1) + ((F.me_range + 3) >> 2) + 2);
     c.spec = spec_in;
 #if defined(__HIP_DEVICE_COMPILE__)
     // (first read after mb_begin's barriers)

@@ -102,7 +102,7 @@ static constexpr uint8_t kBlkX[16] = {0, 4, 0, 4, 8, 12, 8, 12, 0, 4, 0, 4, 8, 1
 static constexpr uint8_t kBlkY[16] = {0, 0, 4, 4, 0, 0, 4, 4, 8, 8, 12, 12, 8, 8, 12, 12};
 // I16x16 DC matrix position of luma block idx (raster index into 4x4 DC matrix)
 static constexpr uint8_t kDcPos[16] = {0, 1, 4, 5, 2, 3, 6, 7, 8, 9, 12, 13, 10, 11, 14, 15};
-HD int blk_idx(int x, int y) { return 8 * (y >> 3) + 4 * (x >> 3) + 2 * ((y & 7) >> 2) + ((x & 7) >> 2); }
+constexpr HD int blk_idx(int x, int y) { return 8 * (y >> 3) + 4 * (x >> 3) + 2 * ((y & 7) >> 2) + ((x & 7) >> 2); }
 // kBlkX / kBlkY as bit arithmetic (no table load for lane-varying indices)
 HD int blk_x(int bi) { return ((bi >> 2) & 1) * 8 + (bi & 1) * 4; }
 HD int blk_y(int bi) { return ((bi >> 3) & 1) * 8 + ((bi >> 1) & 1) * 4; }
@@ -410,6 +410,15 @@ HD void unscan(const T* list, int* m)
 #pragma unroll
     for (int i = 0; i < 16; ++i) m[kZigzag[i]] = list[i];
 }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// set bits of a wave mask below this lane (v_mbcnt: the rank of an enabled
+// lane among the enabled ones)
+__device__ __forceinline__ int lanes_below(unsigned long long m)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+#endif
 
 // Inter-workgroup flags (agent scope, see hl_pipeline.h)
 typedef __attribute__((address_space(1))) int32_t gi32;
