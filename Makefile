@@ -1,6 +1,7 @@
 # Builds (for gfx950):
 #   hartallo_amd/libhartallo_amd.so  the product: HIP kernels + host writer + C ABI
 #   tests/emu/libhl_emu.so           test-only host build of the kernel logic
+#   tests/emu/libhl_pyr_emu.so       test-only host build of the layer pyramid (hl_pyramid.h)
 #   tests/gpu_unit/libhl_unit.so     test-only GPU unit kernels (coop pipeline vs scalar primitives)
 #   tests/gpu_unit/libhl_unit_cand.so  test-only GPU unit kernel (the search's candidate slot)
 #   oracle/...                       test-only CPU oracle and reference build (oracle/Makefile)
@@ -23,7 +24,7 @@ DEVFLAGS := -mllvm -amdgpu-sched-strategy=iterative-ilp
 all: product emu unit oracle sanitize
 
 product: hartallo_amd/libhartallo_amd.so
-emu: tests/emu/libhl_emu.so
+emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so
 unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so
 
 hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
@@ -36,6 +37,10 @@ EMUSRC := tests/emu/hl_emu_search.hip
 EMUINC := tests/emu/hl_emu_ctl.hip tests/emu/hl_emu_memo.hip tests/emu/hl_emu.hip
 tests/emu/libhl_emu.so: $(EMUSRC) $(EMUINC) $(HOSTSRC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -O2 -DHL_FAM3=1 -shared -o $@ $(EMUSRC) $(HOSTSRC)
+
+# the layer pyramid's per-span code on the host (no device code: a plain C++ source for the host compiler)
+tests/emu/libhl_pyr_emu.so: tests/emu/hl_pyr_emu.cpp $(CSRC)/hl_pyramid.h
+	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_pyr_emu.cpp
 
 tests/gpu_unit/libhl_unit.so: tests/gpu_unit/hl_unit.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared -o $@ tests/gpu_unit/hl_unit.hip
@@ -107,5 +112,5 @@ oracle: product  # oracle/_ref/drop_in_enc links the product library
 	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
-	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
+	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
 	$(MAKE) -C oracle clean

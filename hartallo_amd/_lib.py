@@ -78,6 +78,10 @@ EXPORTED_SYMBOLS = (
     "hl_amd_import_layer",
     "hl_amd_svc_layer_ms",
     "hl_amd_encode_layers_batch",
+    "hl_amd_encode_au",
+    "hl_amd_encode_aus_batch",
+    "hl_amd_get_layer_input",
+    "hl_amd_bench_pyramid",
     "hl_amd_version",
 )
 
@@ -280,6 +284,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.hl_amd_import_layer.restype = i32
     lib.hl_amd_encode_layers_batch.argtypes = [vp, i32, i32, pp, ctypes.POINTER(_Result)]
     lib.hl_amd_encode_layers_batch.restype = i32
+    for name, args in (("hl_amd_encode_au", [vp, vp, vp, vp, i32, ctypes.POINTER(_Result)]),
+                       ("hl_amd_encode_aus_batch", [vp, i32, pp, ctypes.POINTER(_Result)]),
+                       ("hl_amd_get_layer_input", [vp, i32, vp, vp, vp]),
+                       ("hl_amd_bench_pyramid", [vp, i32, ctypes.POINTER(ctypes.c_float)])):
+        if hasattr(lib, name):  # (absent from builds before the layer pyramid loaded through HL_LIB)
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = i32
     lib.hl_amd_svc_layer_ms.argtypes = [vp]
     lib.hl_amd_svc_layer_ms.restype = ctypes.c_float
     lib.hl_amd_version.argtypes = []
@@ -673,3 +684,63 @@ class SvcEncoder(Encoder):
         if rc != HL_AMD_SUCCESS:
             raise HlAmdError(rc, "hl_amd_encode_layers_batch")
         return [self._result(r) for r in res]
+
+    def encode_au(self, y, u, v) -> EncodeResult:
+        """One access unit from the top layer's frame alone (host numpy uint8
+        planes): the lower layers' input is derived on the GPU
+        (hl_amd_encode_au).  hdr holds every header set the layers' calls
+        signalled, in order; annexb() is the access unit as a caller of
+        encode_layer assembles it."""
+        import numpy as np
+
+        w, h = self.size(self.layers - 1)
+        ys = [np.ascontiguousarray(p, dtype=np.uint8) for p in (y, u, v)]
+        if ys[0].size != w * h or ys[1].size != w * h // 4 or ys[2].size != ys[1].size:
+            raise HlAmdError(HL_AMD_ERROR_INVALID_FORMAT, "encode_au (plane sizes)")
+        r = _Result()
+        rc = self.lib.hl_amd_encode_au(self._h, ys[0].ctypes.data, ys[1].ctypes.data, ys[2].ctypes.data, 0, ctypes.byref(r))
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_au")
+        return self._result(r)
+
+    def encode_au_device(self, y_ptr: int, u_ptr: int, v_ptr: int, collect: bool = True):
+        """encode_au with the top layer's planes already in device memory."""
+        r = _Result()
+        rc = self.lib.hl_amd_encode_au(self._h, ctypes.c_void_p(y_ptr), ctypes.c_void_p(u_ptr), ctypes.c_void_p(v_ptr), 1, ctypes.byref(r))
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_au")
+        return self._result(r) if collect else r.data_size
+
+    def encode_aus_batch_device(self, ptrs):
+        """n access units from n top-layer frames resident in HBM: ptrs[i] =
+        (y_ptr, u_ptr, v_ptr) of access unit i's frame.  Returns one
+        EncodeResult per access unit (hl_amd_encode_aus_batch)."""
+        n = len(ptrs)
+        flat = (ctypes.c_void_p * (3 * n))(*[ptrs[i][c] for i in range(n) for c in range(3)])
+        res = (_Result * n)()
+        rc = self.lib.hl_amd_encode_aus_batch(self._h, n, flat, res)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_aus_batch")
+        return [self._result(r) for r in res]
+
+    def layer_input(self, layer: int):
+        """The input planes (concatenated Y|U|V) the last encode_au /
+        encode_aus_batch_device derived for `layer`; the top layer's is the
+        frame itself (hl_amd_get_layer_input)."""
+        import numpy as np
+
+        w, h = self.size(layer)
+        n = w * h
+        out = np.empty(n * 3 // 2, np.uint8)
+        rc = self.lib.hl_amd_get_layer_input(self._h, layer, out.ctypes.data, out.ctypes.data + n, out.ctypes.data + n + n // 4)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_get_layer_input")
+        return out
+
+    def bench_pyramid(self, iters: int = 50) -> float:
+        """average ms per launch of k_pyramid on the last encode_au's frame (diagnostics)"""
+        ms = ctypes.c_float()
+        rc = self.lib.hl_amd_bench_pyramid(self._h, iters, ctypes.byref(ms))
+        if rc:
+            raise HlAmdError(rc, "hl_amd_bench_pyramid")
+        return ms.value

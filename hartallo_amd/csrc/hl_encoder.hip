@@ -11,7 +11,8 @@
 //                    workgroup per MB row, LDS tiles, raster causality)
 //   5. host CAVLC serialisation of the MB records (hl_writer.cpp)
 // Runs of pictures: k_pipeline (hl_pipeline.h), one persistent launch.
-// Spatial SVC layers: k_svc_mb, k_deblock_rows, k_el_count / k_el_write.
+// Spatial SVC layers: k_svc_mb, k_deblock_rows, k_el_count / k_el_write; the
+// lower layers' input from the top layer's frame: k_pyramid (hl_pyramid.h).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +35,7 @@
 #if !defined(HL_KERNELS_ONLY)
 #include "hl_svc.h"
 #include "hl_cavlc.h"
+#include "hl_pyramid.h"
 #include "hl_writer.h"
 #endif
 
@@ -2489,6 +2491,16 @@ struct SvcState {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_base = nullptr;
     bool linked = true;
     int pipe_wg = 128;  // workgroups of a batch's base run: the rest of the device codes the enhancement layers
+    // hl_amd_encode_au / hl_amd_encode_aus_batch (k_pyramid, hl_pyramid.h):
+    // the input planes of every layer as last derived (the top layer's: the
+    // frame itself), null before the first such call (hl_amd_get_layer_input)
+    const uint8_t* pyr_in[4][3] = {};
+    std::vector<uint8_t> pyr_hdr;                // every header set the layer calls of the last hl_amd_encode_au signalled
+    uint8_t* d_pyr = nullptr;                    // batch: the lower layers' planes, layer by layer, frame by frame (Y|U|V)
+    size_t pyr_cap = 0;
+    const uint8_t** d_pyr_tab = nullptr;         // batch: the top planes' table on the device [3 * frames]
+    size_t pyr_tab_cap = 0;
+    std::vector<const uint8_t*> pyr_planes;      // batch: the plane table handed to hl_amd_encode_layers_batch
 };
 
 static bool svc_started(const hl_amd_encoder_t* e) { return e->svc && e->svc->started; }
@@ -2521,6 +2533,8 @@ static void svc_free(hl_amd_encoder_t* e)
     (void)hipFree(s->d_unpinned);
     (void)hipFree(s->d_bst);
     (void)hipHostFree(s->h_bst);
+    (void)hipFree(s->d_pyr);
+    (void)hipFree(s->d_pyr_tab);
     if (s->ev_base) (void)hipEventDestroy(s->ev_base);
     if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
     if (s->ev_join) (void)hipEventDestroy(s->ev_join);
@@ -3232,5 +3246,192 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
     }
     restore.ok = rc == HL_AMD_SUCCESS;
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Access units from the top layer's frame alone (no reference interface: the
+// reference's caller scales every layer itself).  k_pyramid (hl_pyramid.h)
+// writes the lower layers' input planes on the encoder's stream -- one launch
+// for every level, plane and frame -- and the access units are coded by the
+// per-layer path (hl_amd_encode_layer) or the layers batch
+// (hl_amd_encode_layers_batch) from those planes: every rule is theirs.
+// ---------------------------------------------------------------------------
+static bool pyr_aligned(const uint8_t* p) { return ((uintptr_t)p & 7) == 0; }
+
+extern "C" int32_t hl_amd_encode_au(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t* u, const uint8_t* v, int32_t on_device,
+                                    hl_amd_result_t* r)
+{
+    if (!e || !y || !u || !v || !r) return HL_AMD_ERROR_INVALID_PARAMETER;
+    SvcState* s = e->svc;
+    if (!s || s->w.size() < 2) return HL_AMD_ERROR_INVALID_STATE;
+    const int layers = (int)s->w.size();
+    if (s->first != 0 || s->last != layers - 1) return HL_AMD_ERROR_INVALID_STATE;  // every layer is derived and coded here
+    if (e->rc) return HL_AMD_ERROR_NOT_IMPLEMENTED;                                  // as the layer calls (svc_start)
+    int32_t rc = svc_start(e);
+    if (rc != HL_AMD_SUCCESS) return rc;
+    if (s->next != s->first || e->broken) return HL_AMD_ERROR_INVALID_STATE;  // inside an access unit of hl_amd_encode_layer calls
+    SvcLayerDev& T = s->el[layers - 2];
+    if (!on_device || !pyr_aligned(y) || !pyr_aligned(u) || !pyr_aligned(v)) {
+        // host planes; device planes k_pyramid's 8-byte loads cannot take are copied too
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        HL_HIP_CHECK(hipMemcpyAsync(T.d_in[0], y, (size_t)T.W * T.H, kind, e->stream));
+        HL_HIP_CHECK(hipMemcpyAsync(T.d_in[1], u, (size_t)T.Wc * T.Hc, kind, e->stream));
+        HL_HIP_CHECK(hipMemcpyAsync(T.d_in[2], v, (size_t)T.Wc * T.Hc, kind, e->stream));
+        y = T.d_in[0];
+        u = T.d_in[1];
+        v = T.d_in[2];
+    }
+    PyrArgs A{};
+    A.src[0] = s->pyr_in[layers - 1][0] = y;
+    A.src[1] = s->pyr_in[layers - 1][1] = u;
+    A.src[2] = s->pyr_in[layers - 1][2] = v;
+    A.W = T.W;
+    A.H = T.H;
+    for (int j = 0; j < layers - 1; ++j) {  // level j + 1 is layer l's input
+        const int l = layers - 2 - j;
+        for (int c = 0; c < 3; ++c) s->pyr_in[l][c] = A.dst[j][c] = l ? s->el[l - 1].d_in[c] : e->d_in[c];
+    }
+    HL_HIP_CHECK(launch_pyramid(A, layers - 1, 1, e->stream));
+    memset(r, 0, sizeof(*r));
+    s->pyr_hdr.clear();
+    for (int l = 0; l < layers; ++l) {
+        hl_amd_result_t t{};
+        rc = hl_amd_encode_layer(e, s->w[l], s->h[l], s->pyr_in[l][0], s->pyr_in[l][1], s->pyr_in[l][2], 1, &t);
+        if (rc != HL_AMD_SUCCESS) return rc;
+        if (t.type & HL_AMD_RESULT_TYPE_HDR) s->pyr_hdr.insert(s->pyr_hdr.end(), t.hdr, t.hdr + t.hdr_size);
+        if (t.type & HL_AMD_RESULT_TYPE_DATA) {
+            r->type |= HL_AMD_RESULT_TYPE_DATA;
+            r->data = t.data;
+            r->data_size = t.data_size;
+        }
+    }
+    if (!s->pyr_hdr.empty()) {
+        r->type |= HL_AMD_RESULT_TYPE_HDR;
+        r->hdr = s->pyr_hdr.data();
+        r->hdr_size = s->pyr_hdr.size();
+    }
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_encode_aus_batch(hl_amd_encoder_t* e, int32_t n, const uint8_t* const* top_planes, hl_amd_result_t* results)
+{
+    if (!e || n <= 0 || !top_planes || !results) return HL_AMD_ERROR_INVALID_PARAMETER;
+    SvcState* s = e->svc;
+    if (!s || s->w.size() < 2) return HL_AMD_ERROR_INVALID_STATE;
+    const int layers = (int)s->w.size();
+    for (int i = 0; i < 3 * n; ++i)
+        if (!top_planes[i] || !pyr_aligned(top_planes[i])) return HL_AMD_ERROR_INVALID_PARAMETER;
+    // hl_amd_encode_layers_batch's refusals, before anything is derived
+    int32_t rc = svc_start(e);
+    if (rc != HL_AMD_SUCCESS) return rc;
+    if (s->first != 0 || s->last != layers - 1 || s->next != 0 || e->broken) return HL_AMD_ERROR_INVALID_STATE;
+    if (e->rc) return HL_AMD_ERROR_NOT_IMPLEMENTED;
+    size_t fb[4], at[4], total = 0;  // per lower layer: bytes of a frame (Y|U|V), offset of its frames in d_pyr
+    for (int l = 0; l < layers - 1; ++l) {
+        fb[l] = (size_t)s->w[l] * s->h[l] * 3 / 2;
+        at[l] = total;
+        total += fb[l] * n;
+    }
+    if (s->pyr_cap < total) {
+        (void)hipFree(s->d_pyr);
+        s->d_pyr = nullptr;
+        s->pyr_cap = 0;
+        if (hipMalloc(&s->d_pyr, total) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        s->pyr_cap = total;
+    }
+    if (s->pyr_tab_cap < (size_t)3 * n) {
+        (void)hipFree(s->d_pyr_tab);
+        s->d_pyr_tab = nullptr;
+        s->pyr_tab_cap = 0;
+        if (hipMalloc(&s->d_pyr_tab, sizeof(uint8_t*) * 3 * n) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        s->pyr_tab_cap = (size_t)3 * n;
+    }
+    HL_HIP_CHECK(hipMemcpyAsync(s->d_pyr_tab, top_planes, sizeof(uint8_t*) * 3 * n, hipMemcpyHostToDevice, e->stream));
+    HL_HIP_CHECK(hipStreamSynchronize(e->stream));  // the caller's table may go once this call returns
+    const int W = s->w[layers - 1], H = s->h[layers - 1];
+    for (int f0 = 0; f0 < n; f0 += 65535) {  // grid z holds the frames
+        PyrArgs A{};
+        A.tab = s->d_pyr_tab + (size_t)3 * f0;
+        A.W = W;
+        A.H = H;
+        for (int j = 0; j < layers - 1; ++j) {
+            const int l = layers - 2 - j;
+            const size_t ys = (size_t)s->w[l] * s->h[l];
+            uint8_t* f = s->d_pyr + at[l] + fb[l] * f0;
+            A.dst[j][0] = f;
+            A.dst[j][1] = f + ys;
+            A.dst[j][2] = f + ys + ys / 4;
+            A.fstride[j] = fb[l];
+        }
+        HL_HIP_CHECK(launch_pyramid(A, layers - 1, std::min(65535, n - f0), e->stream));
+    }
+    s->pyr_planes.resize((size_t)3 * n * layers);
+    for (int l = 0; l < layers; ++l)
+        for (int i = 0; i < n; ++i) {
+            const uint8_t** p = &s->pyr_planes[((size_t)l * n + i) * 3];
+            if (l == layers - 1) {
+                for (int c = 0; c < 3; ++c) p[c] = top_planes[3 * i + c];
+            }
+            else {
+                const size_t ys = (size_t)s->w[l] * s->h[l];
+                p[0] = s->d_pyr + at[l] + fb[l] * i;
+                p[1] = p[0] + ys;
+                p[2] = p[1] + ys / 4;
+            }
+            if (i == n - 1)
+                for (int c = 0; c < 3; ++c) s->pyr_in[l][c] = p[c];
+        }
+    // (the batch orders its two streams after what is queued on the encoder's stream: the pyramid)
+    return hl_amd_encode_layers_batch(e, n, layers, s->pyr_planes.data(), results);
+}
+
+extern "C" int32_t hl_amd_get_layer_input(hl_amd_encoder_t* e, int32_t layer, uint8_t* y, uint8_t* u, uint8_t* v)
+{
+    if (!e || !y || !u || !v) return HL_AMD_ERROR_INVALID_PARAMETER;
+    SvcState* s = e->svc;
+    if (!s || !s->started) return HL_AMD_ERROR_INVALID_STATE;
+    if (layer < 0 || layer >= (int)s->w.size()) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!s->pyr_in[layer][0]) return HL_AMD_ERROR_INVALID_STATE;  // nothing derived yet
+    const size_t ys = (size_t)s->w[layer] * s->h[layer];
+    HL_HIP_CHECK(hipMemcpyAsync(y, s->pyr_in[layer][0], ys, hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipMemcpyAsync(u, s->pyr_in[layer][1], ys / 4, hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipMemcpyAsync(v, s->pyr_in[layer][2], ys / 4, hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipStreamSynchronize(e->stream));
+    return HL_AMD_SUCCESS;
+}
+
+// k_pyramid alone: `iters` launches that derive the lower layers' input of
+// the last hl_amd_encode_au's frame again (the same planes into the same
+// buffers), timed with HIP events on the encoder's stream; *ms = average
+// milliseconds per launch.  Diagnostics, like hl_amd_bench_planes.
+extern "C" int32_t hl_amd_bench_pyramid(hl_amd_encoder_t* e, int32_t iters, float* ms)
+{
+    if (!e || iters <= 0 || !ms) return HL_AMD_ERROR_INVALID_PARAMETER;
+    SvcState* s = e->svc;
+    if (!s || !s->started || s->next != s->first) return HL_AMD_ERROR_INVALID_STATE;
+    const int layers = (int)s->w.size();
+    // the planes of an hl_amd_encode_au call (a batch's lie in its own buffers)
+    if (!s->pyr_in[0][0] || s->pyr_in[0][0] != e->d_in[0]) return HL_AMD_ERROR_INVALID_STATE;
+    PyrArgs A{};
+    A.W = s->w[layers - 1];
+    A.H = s->h[layers - 1];
+    for (int c = 0; c < 3; ++c) {
+        A.src[c] = s->pyr_in[layers - 1][c];
+        for (int j = 0; j < layers - 1; ++j) A.dst[j][c] = const_cast<uint8_t*>(s->pyr_in[layers - 2 - j][c]);
+    }
+    hipEvent_t a, b;
+    HL_HIP_CHECK(hipEventCreate(&a));
+    HL_HIP_CHECK(hipEventCreate(&b));
+    HL_HIP_CHECK(launch_pyramid(A, layers - 1, 1, e->stream));  // warm
+    HL_HIP_CHECK(hipEventRecord(a, e->stream));
+    for (int i = 0; i < iters; ++i) HL_HIP_CHECK(launch_pyramid(A, layers - 1, 1, e->stream));
+    HL_HIP_CHECK(hipEventRecord(b, e->stream));
+    HL_HIP_CHECK(hipEventSynchronize(b));
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, a, b);
+    *ms = t / iters;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return HL_AMD_SUCCESS;
 }
 #endif  // !HL_KERNELS_ONLY

@@ -387,6 +387,56 @@ int32_t hl_amd_import_layer(hl_amd_encoder_t* encoder, int32_t layer, const void
 int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* encoder, int32_t n, int32_t layers, const uint8_t* const* planes,
                                    hl_amd_result_t* results);
 
+/* ---- access units from the top layer's frame ----
+ * No reference interface: the reference's caller scales every layer itself
+ * (its test driver reads one file per layer, test_encoder.c:100-111).  Here
+ * the caller hands over the top layer's frame only and the encoder derives
+ * the lower layers' input on the GPU (k_pyramid, hartallo_amd/csrc/
+ * hl_pyramid.h): layer l = the 2x2 box average (a + b + c + d + 2) >> 2 of
+ * layer l + 1, every plane on its own, rounded at every level -- the filter
+ * of hartallo_amd.synth.svc_clips, so a stream coded from the top clip alone
+ * equals the one coded from svc_clips' layers.
+ *
+ * hl_amd_encode_au: one access unit.  The frame (host planes, or planes in
+ * HBM with on_device) becomes the top layer's input, one k_pyramid launch on
+ * the encoder's stream writes the input planes of the layers below, and the
+ * layers are coded as by hl_amd_encode_layer(..., on_device = 1, ...) for
+ * layer 0, 1, ... -- the GOP counter, idr_pic_id and every other rule are that
+ * call's.  result folds those calls' results: HDR if any of them signalled
+ * it, hdr then every header set they signalled, in order (what a caller of
+ * the layer calls writes out: the reference's driver writes the header bytes
+ * at each such call, test_encoder.c:220-236); DATA the access unit.
+ * HL_AMD_ERROR_INVALID_STATE with fewer than 2 layers, with a layer range
+ * other than all layers (hl_amd_set_layer_range), and between the
+ * hl_amd_encode_layer calls of an unfinished access unit;
+ * HL_AMD_ERROR_NOT_IMPLEMENTED under rate control (as hl_amd_encode_layer).
+ * A refused call leaves the encoder as it was. */
+int32_t hl_amd_encode_au(hl_amd_encoder_t* encoder, const uint8_t* y, const uint8_t* u, const uint8_t* v, int32_t on_device,
+                         hl_amd_result_t* result);
+
+/* n access units from n top-layer frames in HBM (top_planes[3 * i + c] =
+ * plane c of access unit i's frame, 8-byte aligned): one k_pyramid launch
+ * derives the lower layers' planes of all n frames into device buffers the
+ * encoder owns, then the access units are coded by
+ * hl_amd_encode_layers_batch: its results, its failure contract and its
+ * refusals.  No reference interface. */
+int32_t hl_amd_encode_aus_batch(hl_amd_encoder_t* encoder, int32_t n, const uint8_t* const* top_planes, hl_amd_result_t* results);
+
+/* the input planes the last hl_amd_encode_au derived for `layer` (for the top
+ * layer: the frame itself), copied to the host; after hl_amd_encode_aus_batch
+ * those of its last frame.  A top frame handed over in HBM is read from the
+ * caller's planes, which must still be there.  Valid until the next encode
+ * call.
+ * HL_AMD_ERROR_INVALID_STATE before the first such call.  For callers who
+ * want the thumbnails, and for the tests.  No reference interface. */
+int32_t hl_amd_get_layer_input(hl_amd_encoder_t* encoder, int32_t layer, uint8_t* y, uint8_t* u, uint8_t* v);
+
+/* Diagnostics: `iters` launches of k_pyramid on the frame of the last
+ * hl_amd_encode_au (the same planes into the same buffers); *ms = average ms
+ * per launch.  HL_AMD_ERROR_INVALID_STATE without such a call.  No reference
+ * interface. */
+int32_t hl_amd_bench_pyramid(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
+
 /* device time (ms) of the enhancement layers of the last access unit (with
  * hl_amd_set_timing on) */
 float hl_amd_svc_layer_ms(hl_amd_encoder_t* encoder);
