@@ -2,8 +2,10 @@
 #   hartallo_amd/libhartallo_amd.so  the product: HIP kernels + host writer + C ABI
 #   tests/emu/libhl_emu.so           test-only host build of the kernel logic
 #   tests/emu/libhl_pyr_emu.so       test-only host build of the layer pyramid (hl_pyramid.h)
+#   tests/emu/libhl_rec_emu.so       test-only host exports of the candidate record's pack / unpack (hl_mbcore.h)
 #   tests/gpu_unit/libhl_unit.so     test-only GPU unit kernels (coop pipeline vs scalar primitives)
 #   tests/gpu_unit/libhl_unit_cand.so  test-only GPU unit kernel (the search's candidate slot)
+#   tests/gpu_unit/libhl_unit_rec.so   test-only GPU unit kernel (the search's candidate record and selection)
 #   oracle/...                       test-only CPU oracle and reference build (oracle/Makefile)
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
@@ -24,8 +26,8 @@ DEVFLAGS := -mllvm -amdgpu-sched-strategy=iterative-ilp
 all: product emu unit oracle sanitize
 
 product: hartallo_amd/libhartallo_amd.so
-emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so
-unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so
+emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_rec_emu.so
+unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so
 
 hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -shared -o $@ $(KSRC) $(HOSTSRC)
@@ -42,11 +44,18 @@ tests/emu/libhl_emu.so: $(EMUSRC) $(EMUINC) $(HOSTSRC) $(HDRS)
 tests/emu/libhl_pyr_emu.so: tests/emu/hl_pyr_emu.cpp $(CSRC)/hl_pyramid.h
 	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_pyr_emu.cpp
 
+# the candidate record's pack and unpack functions on the host (no device code)
+tests/emu/libhl_rec_emu.so: tests/emu/hl_rec_emu.hip $(HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -O2 --cuda-host-only -shared -o $@ tests/emu/hl_rec_emu.hip
+
 tests/gpu_unit/libhl_unit.so: tests/gpu_unit/hl_unit.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared -o $@ tests/gpu_unit/hl_unit.hip
 
 tests/gpu_unit/libhl_unit_cand.so: tests/gpu_unit/hl_unit_cand.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared -o $@ tests/gpu_unit/hl_unit_cand.hip
+
+tests/gpu_unit/libhl_unit_rec.so: tests/gpu_unit/hl_unit_rec.hip $(HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared -o $@ tests/gpu_unit/hl_unit_rec.hip
 
 # sanitizer builds of the host code (tests/test_sanitizers.py, CPU):
 #   tests/sanitize/libhl_emu_asan.so  the emulator (the kernel logic on the
@@ -112,5 +121,5 @@ oracle: product  # oracle/_ref/drop_in_enc links the product library
 	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
-	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
+	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_rec_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
 	$(MAKE) -C oracle clean

@@ -107,6 +107,38 @@ constexpr int kMbRows = kMbThreads / 16;           // 16-lane rows
 // speculative (see search_partition); at most kMaxPass rows per lane.
 constexpr int kMaxCand = 32;
 constexpr int kMaxSeg = 4;
+// A candidate's result of an evaluation pass (Shared::cd), one 16-byte record:
+// one LDS store by its writer, one LDS load by the selection, and three
+// words for take() to broadcast.  The fields are narrow: bits < 2^15 and
+// dist < 2^17 for a whole MB (phase 2 sums them as this very word), cbp one
+// bit per 4x4 block, single a sum of at most 16 per-block counters of at most
+// 14, last -1..15 stored as last + 1.
+//   bd   = bits | dist << 15
+//   meta = cbp | single << 16 | (last + 1) << 24
+struct alignas(16) CandRec {
+    double cost;
+    uint32_t bd, meta;
+};
+constexpr int kRecBitsW = 15, kRecDistW = 17, kRecCbpW = 16, kRecSingleW = 8, kRecLastW = 5;
+static_assert(kRecBitsW + kRecDistW == 32, "CandRec::bd");
+static_assert(kRecCbpW + kRecSingleW + kRecLastW <= 32, "CandRec::meta");
+static_assert(16 * 14 < (1 << kRecSingleW), "single: 16 blocks' counters of at most 14");
+static_assert(15 + 1 < (1 << kRecLastW), "last + 1: 0..16");
+static_assert(sizeof(CandRec) == 16, "one 16-byte LDS access");
+HD constexpr uint32_t rec_bd(int bits, int dist) { return (uint32_t)bits | (uint32_t)dist << kRecBitsW; }
+HD constexpr uint32_t rec_meta(int cbp, int single, int last)
+{
+    return (uint32_t)cbp | (uint32_t)single << kRecCbpW | (uint32_t)(last + 1) << (kRecCbpW + kRecSingleW);
+}
+HD constexpr int rec_bits(uint32_t bd) { return (int)(bd & ((1u << kRecBitsW) - 1u)); }
+HD constexpr int rec_dist(uint32_t bd) { return (int)(bd >> kRecBitsW); }
+HD constexpr int rec_cbp(uint32_t meta) { return (int)(meta & ((1u << kRecCbpW) - 1u)); }
+HD constexpr int rec_single(uint32_t meta) { return (int)((meta >> kRecCbpW) & ((1u << kRecSingleW) - 1u)); }
+HD constexpr int rec_last(uint32_t meta) { return (int)(meta >> (kRecCbpW + kRecSingleW)) - 1; }
+// the writers' one store (eval_candidates)
+HD void rec_store(CandRec& r, double cost, uint32_t bd, uint32_t meta) { r = CandRec{cost, bd, meta}; }
+static_assert(rec_bits(rec_bd(0x7FFF, 0)) == 0x7FFF && rec_dist(rec_bd(0x7FFF, 0)) == 0, "bits stays out of dist");
+static_assert(rec_last(rec_meta(0xFFFF, 224, -1)) == -1 && rec_single(rec_meta(0, 224, 15)) == 224, "meta fields");
 // partitions whose passes chain speculative steps: with the quad pipeline a
 // pass holds 256 blocks, so even a 16x16 chain (MVP/(0,0) + integer + half
 // step, 16 candidates) fits one pass
@@ -336,10 +368,7 @@ struct Shared {
     CoopTables ct;
     uint32_t qtab[16];                                   // packed quarter-pel phase table
     alignas(8) int2 qoff[16];  // per phase: plane offsets of the two prediction samples relative to (X, Y) (put_cand)
-    struct CandRes {
-        double cost[kMaxCand];
-        int32_t bits[kMaxCand], dist[kMaxCand], single[kMaxCand], cbp[kMaxCand], last[kMaxCand];
-    } cd[2];  // per candidate of a step [parity]
+    CandRec cd[2][kMaxCand];  // per candidate of a step [parity]
     // --- per (sub)partition search results
     double bcost[4][4];
     int32_t bdist[4][4], bsingle[4][4], bcbp[4][4];
@@ -1435,7 +1464,7 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
     Shared& S = c.S;
     c.par ^= 1;
     c.p3 = c.p3 == 2 ? 0 : c.p3 + 1;
-    Shared::CandRes& R = S.cd[c.par];
+    CandRec(&R)[kMaxCand] = S.cd[c.par];
     uint8_t(&tcb)[16][kMaxCand] = S.be_tcb[c.par];
     HL_PROF_T(tp0);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1473,12 +1502,9 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
                 int bits = 0;
                 if (tc) bits = rest + ((w2 >> (5 * (nc1 < 2 ? 0 : (nc1 < 4 ? 1 : (nc1 < 8 ? 2 : 3))))) & 31);
                 const CandSlot cs = S.wc[wave][ci];
-                R.cost[ci] = mv_cost(F, dist, bits, cs.mvx, cs.mvy, pmv);
-                R.bits[ci] = bits;
-                R.dist[ci] = dist;
-                R.single[ci] = tc ? sctr : 0;
-                R.cbp[ci] = tc ? 1 << g.bi : 0;
-                R.last[ci] = tc ? sctr : -1;
+                // (sctr + 1 is w0's own field: the record's last + 1)
+                rec_store(R[ci], mv_cost(F, dist, bits, cs.mvx, cs.mvy, pmv), rec_bd(bits, dist),
+                          tc ? rec_meta(1 << g.bi, sctr, sctr) : rec_meta(0, 0, -1));
             }
         };
         // The memo (Shared::memo; key layout at kMemoSlots).  Every quad probes
@@ -1756,19 +1782,15 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
             }
         }
         // bits (< 2^15 over 16 blocks) and distortion (< 2^17) in one row sum
-        const uint32_t pk = (uint32_t)row_sum((int)((uint32_t)bits | ((uint32_t)dist << 15)));
-        bits = (int)(pk & 0x7FFFu);
-        dist = (int)(pk >> 15);
+        // (the record's bd as it comes out of the sum; cs_sum is the record's
+        // cbp | single << 16, the blocks' bits being distinct)
+        static_assert(kRecCbpW == 16, "cs_sum = 1 << bi | sctr << 16");
+        const uint32_t pk = (uint32_t)row_sum((int)rec_bd(bits, dist));
         cs_sum = row_sum(cs_sum);
         last = row_max(last);
-        if (k0 == 0) {
-            R.cost[ci] = mv_cost(F, dist, bits, cs.mvx, cs.mvy, pmv);
-            R.bits[ci] = bits;
-            R.dist[ci] = dist;
-            R.single[ci] = cs_sum >> 16;
-            R.cbp[ci] = cs_sum & 0xFFFF;
-            R.last[ci] = last ? (last & 15) : -1;
-        }
+        if (k0 == 0)
+            rec_store(R[ci], mv_cost(F, rec_dist(pk), rec_bits(pk), cs.mvx, cs.mvy, pmv), pk,
+                      (uint32_t)cs_sum | rec_meta(0, 0, last ? (last & 15) : -1));
     }
     if (g.nblk > 1) HL_SYNC();
     HL_PROF_ADD(c, 1, tp1);
@@ -1928,12 +1950,7 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
                 last = S.be_sctr[t][k];
             }
         }
-        R.cost[t] = mv_cost(F, dist, bits, S.wc[0][t].mvx, S.wc[0][t].mvy, pmv);
-        R.bits[t] = bits;
-        R.dist[t] = dist;
-        R.single[t] = single;
-        R.cbp[t] = cbp;
-        R.last[t] = last;
+        rec_store(R[t], mv_cost(F, dist, bits, S.wc[0][t].mvx, S.wc[0][t].mvy, pmv), rec_bd(bits, dist), rec_meta(cbp, single, last));
     }
 #endif
 }
@@ -1943,16 +1960,15 @@ HD void eval_candidates(Ctx& c, const PartGeo& g, int ncand, const int pmv[2])
 // every block = its last writer (residual.c:796-806); rdo.Single_ctr = the
 // last candidate that wrote it (residual.c:881-897).  The next reader of
 // S.tc is behind a barrier.
-// last_l: candidate (tid & 31)'s R.last when the caller has it in a register
-// (device; -2 = read it here)
 template <bool REC = false>
-HD void commit_candidates(Ctx& c, const PartGeo& g, int n, int last_l = -1, bool by_lane = false)
+HD void commit_candidates(Ctx& c, const PartGeo& g, int n, uint32_t meta_l = 0, bool by_lane = false)
 {
-    // by_lane (device): last_l is the lane's own value of CandRes::last for a
-    // candidate below n, else -1, the lanes in the candidates' order
-    // (search_partition holds a pass's results that way); otherwise read here
+    // by_lane (device): meta_l is the lane's own CandRec::meta for a
+    // candidate below n, else 0 (last = -1), the lanes in the candidates'
+    // order (search_partition holds a pass's results that way); otherwise
+    // read here
     Shared& S = c.S;
-    const Shared::CandRes& R = S.cd[c.par];
+    const CandRec(&R)[kMaxCand] = S.cd[c.par];
     HL_PROF_T(tp2);
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint8_t(&tcb)[16][kMaxCand] = S.be_tcb[c.par];
@@ -1968,12 +1984,12 @@ HD void commit_candidates(Ctx& c, const PartGeo& g, int n, int last_l = -1, bool
     }
     {  // last candidate that wrote the counter (vectorised over the pass)
         const int l = c.tid & 31;
-        const int v = by_lane ? last_l : (l < n ? R.last[l] : -1);
+        const int v = rec_last(by_lane ? meta_l : (l < n ? R[l].meta : 0u));
         const unsigned long long bal = __ballot(v >= 0) & (by_lane ? ~0ull : 0xFFFFFFFFull);
         if (bal) chain_write(c, __builtin_amdgcn_readlane(v, 63 - __clzll((long long)bal)));
     }
 #else
-    (void)last_l;
+    (void)meta_l;
     (void)by_lane;
     for (int k = 0; k < g.nblk; ++k) {
         const int hx = k % g.nbw, hy = k / g.nbw;
@@ -1986,8 +2002,8 @@ HD void commit_candidates(Ctx& c, const PartGeo& g, int n, int last_l = -1, bool
             }
     }
     for (int ci = n - 1; ci >= 0; --ci)
-        if (R.last[ci] >= 0) {
-            chain_write(c, R.last[ci]);
+        if (rec_last(R[ci].meta) >= 0) {
+            chain_write(c, rec_last(R[ci].meta));
             break;
         }
 #endif
@@ -2002,7 +2018,7 @@ HD int pick_first_min(const Ctx& c, int lo, int hi, double& m)  // candidates [l
 #if defined(__HIP_DEVICE_COMPILE__)
     const int l = c.tid & 31;
     const bool in = l >= lo && l < hi;
-    const double v = in ? S.cd[c.par].cost[l] : 1.7976931348623157e308;
+    const double v = in ? S.cd[c.par][l].cost : 1.7976931348623157e308;
     double mn = row_min_f64(v);
     mn = fmin(mn, __shfl_xor(mn, 16, 64));  // both 16-lane rows of the half-wave
     const unsigned long long bal = __ballot(in && v == mn) & 0xFFFFFFFFull;
@@ -2010,10 +2026,10 @@ HD int pick_first_min(const Ctx& c, int lo, int hi, double& m)  // candidates [l
     return uni(__ffsll((long long)bal) - 1);
 #else
     int bi = lo;
-    m = S.cd[c.par].cost[lo];
+    m = S.cd[c.par][lo].cost;
     for (int ci = lo + 1; ci < hi; ++ci)
-        if (S.cd[c.par].cost[ci] < m) {
-            m = S.cd[c.par].cost[ci];
+        if (S.cd[c.par][ci].cost < m) {
+            m = S.cd[c.par][ci].cost;
             bi = ci;
         }
     return bi;
@@ -2025,6 +2041,70 @@ struct Best {
     double cost;
     int dist, single, cbp, mv[2];
 };
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// The selection's view of a pass (search_partition): the pass's results in
+// the layout its candidates were generated in.  Lane 16 j + i of every wave
+// holds point i of step j; its candidate is the number of enabled lanes
+// below it (candidates are numbered in lane order), so each step of the
+// chain lies in a DPP row of its own.  A lane without a candidate holds the
+// largest double and ci = kMaxCand.
+struct SelRec {
+    double cost;
+    uint32_t bd, meta;  // CandRec's
+    uint32_t mv;        // the slot's MV as it lies in CandSlot: mvx | mvy << 16
+    int ci;
+};
+static_assert(offsetof(CandSlot, mvx) % 4 == 0 && offsetof(CandSlot, mvy) == offsetof(CandSlot, mvx) + 2, "SelRec::mv");
+// gen: the lanes whose point the pass evaluates (uniform)
+__device__ __forceinline__ SelRec sel_load(const Shared& S, int par, int wave, unsigned long long gen, int lane)
+{
+    const bool en = (gen >> lane) & 1;
+    const int ci = en ? lanes_below(gen) : 0;
+    const CandRec r = S.cd[par][ci];
+    SelRec pv;
+    __builtin_memcpy(&pv.mv, &S.wc[wave][ci].mvx, 4);
+    pv.cost = en ? r.cost : 1.7976931348623157e308;
+    pv.bd = r.bd;
+    pv.meta = r.meta;
+    pv.ci = en ? ci : kMaxCand;
+    return pv;
+}
+// The sequential strict-< scans of every step of the chain (me_ds.c:339-347)
+// at once: one DPP row minimum serves the four steps, then each step's
+// smallest cost and the first lane holding it (the lowest lane is the lowest
+// candidate) as uniform values.  Resolving the chain is then scalar work.  A
+// step the pass does not hold has no enabled lane: the largest double, lane -1.
+__device__ __forceinline__ void sel_minima(const SelRec& pv, double (&sm)[kMaxSeg], int (&sb)[kMaxSeg])
+{
+    const double rm = row_min_f64(pv.cost);
+    const unsigned long long b0 = __builtin_bit_cast(unsigned long long, rm);
+    const unsigned long long eq = __ballot(pv.ci != kMaxCand && pv.cost == rm);
+#pragma unroll
+    for (int j = 0; j < kMaxSeg; ++j) {
+        sm[j] = __builtin_bit_cast(double, (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(b0 >> 32), 16 * j) << 32 |
+                                               (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b0, 16 * j));
+        const unsigned e16 = (unsigned)(eq >> (16 * j)) & 0xFFFFu;
+        sb[j] = e16 ? 16 * j + __ffs((int)e16) - 1 : -1;
+    }
+}
+// The winner in lane bi becomes the search's best: three words broadcast and
+// unpacked on the scalar side.  Returns its diamond point, which is the
+// lane's place in its row (what put_cand stored as the slot's point).
+__device__ __forceinline__ int sel_take(const SelRec& pv, int bi, double m, Best& b)
+{
+    const uint32_t bd = (uint32_t)__builtin_amdgcn_readlane((int)pv.bd, bi);
+    const uint32_t meta = (uint32_t)__builtin_amdgcn_readlane((int)pv.meta, bi);
+    const uint32_t mv = (uint32_t)__builtin_amdgcn_readlane((int)pv.mv, bi);
+    b.cost = m;
+    b.single = rec_single(meta);
+    b.dist = rec_dist(bd);
+    b.cbp = rec_cbp(meta);
+    b.mv[0] = (int16_t)(mv & 0xFFFFu);
+    b.mv[1] = (int)mv >> 16;
+    return bi & 15;
+}
+#endif
 
 // Pipelined runs (hl_pipeline.h): the task of a picture after which the
 // quarter-pel planes of all its MBs (X' <= X, Y' <= Y) are final.  Plane
@@ -2120,12 +2200,13 @@ HD bool search_partition(Ctx& c, int j, int pi, int spi, bool probe)
             put_cand(c, g.px, g.py, g.pw, g.ph, 0, pmv[0], pmv[1], 0, (c.tid & 63) == 0);
             eval_candidates<REC>(c, g, 1, pmv);
             commit_candidates<REC>(c, g, 1);
-            if (uni(S.cd[c.par].bits[0]) == 0 || uni(S.cd[c.par].single[0]) < 6) {
+            const uint32_t bd0 = (uint32_t)uni((int)S.cd[c.par][0].bd), meta0 = (uint32_t)uni((int)S.cd[c.par][0].meta);
+            if (rec_bits(bd0) == 0 || rec_single(meta0) < 6) {
                 probably = true;
                 b.cost = 0.0;
-                b.single = uni(S.cd[c.par].single[0]);
-                b.dist = uni(S.cd[c.par].dist[0]);
-                b.cbp = uni(S.cd[c.par].cbp[0]);
+                b.single = rec_single(meta0);
+                b.dist = rec_dist(bd0);
+                b.cbp = rec_cbp(meta0);
                 b.mv[0] = pmv[0];
                 b.mv[1] = pmv[1];
             }
@@ -2192,24 +2273,18 @@ HD bool search_partition(Ctx& c, int j, int pi, int spi, bool probe)
     // a pass's candidate results, each lane holding the candidate it
     // generated (pv_ci; kMaxCand: none): loaded once per pass, then every
     // pick and take is register work (bi = the candidate's lane)
-    double pv_cost = 0.0;
-    int pv_single = 0, pv_dist = 0, pv_cbp = 0, pv_mvx = 0, pv_mvy = 0, pv_pad = 0, pv_last = -1, pv_ci = kMaxCand;
+    // (the record's cost, bd and meta, and the slot's MV as the one word it
+    // is in CandSlot, mvx | mvy << 16; the point index is the lane's own)
+    SelRec pv = {0.0, 0u, 0u, 0u, kMaxCand};
     unsigned long long gen = 0;  // the lanes whose point the pass evaluates (uniform)
-    auto take = [&](int bi, double m) {
-        b.cost = m;
-        b.single = __builtin_amdgcn_readlane(pv_single, bi);
-        b.dist = __builtin_amdgcn_readlane(pv_dist, bi);
-        b.cbp = __builtin_amdgcn_readlane(pv_cbp, bi);
-        b.mv[0] = __builtin_amdgcn_readlane(pv_mvx, bi);
-        b.mv[1] = __builtin_amdgcn_readlane(pv_mvy, bi);
-        return __builtin_amdgcn_readlane(pv_pad, bi);
-    };
+    auto take = [&](int bi, double m) { return sel_take(pv, bi, m, b); };
 #else
     auto take = [&](int bi, double m) {
+        const CandRec r = S.cd[c.par][bi];
         b.cost = m;
-        b.single = uni(S.cd[c.par].single[bi]);
-        b.dist = uni(S.cd[c.par].dist[bi]);
-        b.cbp = uni(S.cd[c.par].cbp[bi]);
+        b.single = rec_single(r.meta);
+        b.dist = rec_dist(r.bd);
+        b.cbp = rec_cbp(r.meta);
         b.mv[0] = uni((int)S.wc[c.tid >> 6][bi].mvx);
         b.mv[1] = uni((int)S.wc[c.tid >> 6][bi].mvy);
         return uni(S.wc[c.tid >> 6][bi].pad & 15);
@@ -2258,10 +2333,15 @@ HD bool search_partition(Ctx& c, int j, int pi, int spi, bool probe)
             const int mx = s3 ? ((i & 15) ? 0 : pmv[0]) : dmx, my = s3 ? ((i & 15) ? 0 : pmv[1]) : dmy;
             const int sh = st == 2 ? 2 : (st == 1 ? 1 : 0);
             const unsigned long long bal = __ballot(en);
-            for (int k = 0; k < kMaxSeg; ++k) {
-                lo[k] = __popcll(bal & ((1ull << (16 * k)) - 1ull));
-                n[k] = __popcll(bal & (0xFFFFull << (16 * k)));
-            }
+            // the four rows' counts, 32-bit scalar work; lo = their running sum
+            const uint32_t bl = (uint32_t)bal, bh = (uint32_t)(bal >> 32);
+            n[0] = __popc(bl & 0xFFFFu);
+            n[1] = __popc(bl >> 16);
+            n[2] = __popc(bh & 0xFFFFu);
+            n[3] = __popc(bh >> 16);
+            lo[1] = n[0];
+            lo[2] = n[0] + n[1];
+            lo[3] = lo[2] + n[2];
             if (en) put_cand(c, g.px, g.py, g.pw, g.ph, lanes_below(bal), mx * (1 << sh), my * (1 << sh), i & 15, true);
             gen = bal;
         }
@@ -2310,41 +2390,10 @@ HD bool search_partition(Ctx& c, int j, int pi, int spi, bool probe)
         // candidate is the number of enabled lanes below it, and candidates
         // are numbered in lane order), so each step of the chain lies in a DPP
         // row of its own.
-        const bool pv_en = (gen >> (c.tid & 63)) & 1;
-        {
-            const int ci = pv_en ? lanes_below(gen) : 0;
-            const Shared::CandRes& R = S.cd[c.par];
-            const CandSlot cs = S.wc[c.tid >> 6][ci];
-            pv_cost = pv_en ? R.cost[ci] : 1.7976931348623157e308;
-            pv_single = R.single[ci];
-            pv_dist = R.dist[ci];
-            pv_cbp = R.cbp[ci];
-            pv_last = R.last[ci];
-            pv_ci = pv_en ? ci : kMaxCand;
-            pv_mvx = cs.mvx;
-            pv_mvy = cs.mvy;
-            pv_pad = cs.pad & 15;
-        }
-        // The sequential strict-< scans of every step of the chain
-        // (me_ds.c:339-347) at once: one DPP row minimum serves the four
-        // steps, then each step's smallest cost and the first lane holding it
-        // (the lowest lane is the lowest candidate) as uniform values.
-        // Resolving the chain below is then scalar work.  A step the pass
-        // does not hold has no enabled lane: the largest double, lane -1.
+        pv = sel_load(S, c.par, c.tid >> 6, gen, c.tid & 63);
         double sm[kMaxSeg];
         int sb[kMaxSeg];
-        {
-            const double rm = row_min_f64(pv_cost);
-            const unsigned long long b0 = __builtin_bit_cast(unsigned long long, rm);
-            const unsigned long long eq = __ballot(pv_en && pv_cost == rm);
-#pragma unroll
-            for (int j = 0; j < kMaxSeg; ++j) {
-                sm[j] = __builtin_bit_cast(double, (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(b0 >> 32), 16 * j) << 32 |
-                                                       (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b0, 16 * j));
-                const unsigned e16 = (unsigned)(eq >> (16 * j)) & 0xFFFFu;
-                sb[j] = e16 ? 16 * j + __ffs((int)e16) - 1 : -1;
-            }
-        }
+        sel_minima(pv, sm, sb);
 #if defined(HL_STEP_PROF)
         HL_PROF_ADD(c, 15, tsel);  // results loaded, the steps' minima found
         HL_PROF_T(tres);
@@ -2429,7 +2478,7 @@ HD bool search_partition(Ctx& c, int j, int pi, int spi, bool probe)
 #if defined(HL_STEP_PROF)
         HL_PROF_ADD(c, 18, tres);  // the chain resolved
 #endif
-        if (used) commit_candidates<REC>(c, g, used, pv_ci < used ? pv_last : -1, true);
+        if (used) commit_candidates<REC>(c, g, used, pv.ci < used ? pv.meta : 0u, true);
 #else
         if (used) commit_candidates<REC>(c, g, used);
 #endif

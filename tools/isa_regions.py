@@ -1,7 +1,7 @@
 """Static instruction counts of k_pipeline's partition search, per source
 region (no GPU needed).
 
-  python tools/isa_regions.py [--asm file.s] [--kernel substring] [--fam3]
+  python tools/isa_regions.py [--asm file.s] [--kernel substring] [--fam3] [--root other-checkout]
 
 Builds the gfx950 assembly of hl_encoder.hip (--fam3: hl_encoder_fam3.hip)
 with the product's flags plus -gline-tables-only, or reads one built before,
@@ -30,6 +30,8 @@ FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC", "-ffp-contract=o
 
 # (anchor, region) in the order of hl_mbcore.h; None = not part of the search
 ANCHORS = [
+    (r"^// A candidate's result of an evaluation pass", "record"),  # CandRec's pack and unpack, inlined into every user
+    (r"^// partitions whose passes chain speculative steps", None),
     (r"^// log2 of a power of two", "search prologue"),          # lg2, part_x .. sub_y
     (r"^HD void sub_part_idx\(", None),
     (r"^struct MvN \{", "mvp"),                                   # mv_at, nb_motion, median3, mvp
@@ -45,8 +47,12 @@ ANCHORS = [
     (r"^\s+// phase 2: one row per candidate", "cost phase"),
     (r"^HD void commit_candidates\(", "commit"),
     (r"^HD int pick_first_min\(", None),
+    (r"^// The selection's view of a pass", "minima"),            # sel_load, sel_minima
+    (r"^// The winner in lane bi becomes the search's best", "resolution"),  # sel_take
     (r"^// Pipelined runs \(hl_pipeline\.h\): the task of a picture", "search prologue"),  # reach_task, reach_wait
     (r"^HD bool search_partition\(", "search prologue"),
+    (r"^    auto take = \[&\]\(int bi, double m\)", "resolution"),  # the winner's broadcast (trees that have it here)
+    (r"^    // first step of stage st from best MV", "search prologue"),
     (r"^    while \(stage >= 0\) \{", "generation"),
     (r"^        const int total = lo\[nseg - 1\]", "probe/emit"),  # the call of eval_candidates
     (r"^        HL_PROF_T\(tsel\);", "minima"),
@@ -56,7 +62,7 @@ ANCHORS = [
     (r"^// Intra prediction \(8\.3", None),
 ]
 REGIONS = ["search prologue", "mvp", "generation", "put_cand", "probe/emit", "miss path", "cost phase", "minima", "resolution", "commit",
-           "search end"]
+           "record", "search end"]
 CLASSES = ["VALU", "SALU", "LDS", "VMEM", "readlane", "branch", "waitcnt", "other"]
 
 
@@ -129,14 +135,15 @@ def main():
     ap.add_argument("--asm")
     ap.add_argument("--kernel", default="k_pipeline")
     ap.add_argument("--fam3", action="store_true")
+    ap.add_argument("--root", default=ROOT, help="another checkout of the project (same anchors: a like-for-like comparison)")
     a = ap.parse_args()
-    regs = line_regions(os.path.join(ROOT, "hartallo_amd", "csrc", "hl_mbcore.h"))
+    regs = line_regions(os.path.join(a.root, "hartallo_amd", "csrc", "hl_mbcore.h"))
     if a.asm:
         asm = open(a.asm).read().splitlines()
     else:
         with tempfile.TemporaryDirectory() as td:
             out = os.path.join(td, "k.s")
-            src = os.path.join(ROOT, "hartallo_amd", "csrc", "hl_encoder_fam3.hip" if a.fam3 else "hl_encoder.hip")
+            src = os.path.join(a.root, "hartallo_amd", "csrc", "hl_encoder_fam3.hip" if a.fam3 else "hl_encoder.hip")
             subprocess.run([HIPCC] + FLAGS + ["-o", out, src], check=True)
             asm = open(out).read().splitlines()
     counts, total = count(asm, a.kernel, regs)
