@@ -1,5 +1,5 @@
 # Builds (for gfx950):
-#   hartallo_amd/libhartallo_amd.so  the product: HIP kernels + host writer + C ABI
+#   hartallo_amd/libhartallo_amd.so  the product: HIP kernels (k_pipeline in three builds) + host writer + C ABI
 #   tests/emu/libhl_emu.so           test-only host build of the kernel logic
 #   tests/emu/libhl_pyr_emu.so       test-only host build of the layer pyramid (hl_pyramid.h)
 #   tests/emu/libhl_rec_emu.so       test-only host exports of the candidate record's pack / unpack (hl_mbcore.h)
@@ -13,8 +13,9 @@ CSRC    := hartallo_amd/csrc
 REF     ?= /root/reference
 HDRS    := $(wildcard $(CSRC)/*.h) include/hartallo_amd.h
 HOSTSRC := $(CSRC)/hl_writer.cpp $(CSRC)/hl_rc.cpp
-# the product kernels, and k_pipeline again with the 8x8-family helpers (runs of one picture)
-KSRC    := $(CSRC)/hl_encoder.hip $(CSRC)/hl_encoder_fam3.hip
+# the product kernels, k_pipeline again with the 8x8-family helpers (runs of one picture)
+# and once more with 256-lane workgroups (two macroblocks per CU)
+KSRC    := $(CSRC)/hl_encoder.hip $(CSRC)/hl_encoder_fam3.hip $(CSRC)/hl_encoder_t256.hip
 # -ffp-contract=off: the RDO costs are IEEE double and must round exactly like the reference
 CXXFLAGS := -std=c++17 -O3 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Wno-unused-variable
 # device code scheduling of the product: the ILP-iterative strategy shortens

@@ -52,6 +52,10 @@ EXPORTED_SYMBOLS = (
     "hl_amd_set_max_ref_frame",
     "hl_amd_last_qp",
     "hl_amd_pipeline_occupancy",
+    "hl_amd_set_pipeline_build",
+    "hl_amd_last_pipeline_build",
+    "hl_amd_pipeline_build_choice",
+    "hl_amd_pipeline_build_threshold",
     "hl_amd_bench_planes",
     "hl_amd_get_recon",
     "hl_amd_set_timing",
@@ -236,6 +240,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.hl_amd_last_qp.restype = i32
     lib.hl_amd_pipeline_occupancy.argtypes = []
     lib.hl_amd_pipeline_occupancy.restype = i32
+    for name, args in (("hl_amd_set_pipeline_build", [vp, i32]), ("hl_amd_last_pipeline_build", [vp]),
+                       ("hl_amd_pipeline_build_choice", [i32, i32, i32]), ("hl_amd_pipeline_build_threshold", [])):
+        if hasattr(lib, name):  # (absent from builds before round 10 loaded through HL_LIB)
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = i32
     lib.hl_amd_bench_planes.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_float)]
     lib.hl_amd_bench_planes.restype = i32
     lib.hl_amd_get_recon.argtypes = [vp, vp, vp, vp]
@@ -480,6 +489,18 @@ class Encoder:
         rc = self.lib.hl_amd_set_pipeline(self._h, workgroups, reach, window)
         if rc != HL_AMD_SUCCESS:
             raise HlAmdError(rc, "hl_amd_set_pipeline")
+
+    def set_pipeline_build(self, mode: int):
+        """hl_amd_set_pipeline_build: 0 chosen per run, 1 the 512-lane build,
+        2 the 256-lane build for every run of more than one picture."""
+        rc = self.lib.hl_amd_set_pipeline_build(self._h, mode)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_set_pipeline_build")
+
+    def last_pipeline_build(self) -> int:
+        """The build the last pipelined run launched (0 with the 8x8-family
+        helper tasks, 1 512-lane, 2 256-lane; -1 before any run)."""
+        return self.lib.hl_amd_last_pipeline_build(self._h)
 
     def recon(self):
         import numpy as np

@@ -899,6 +899,32 @@ __global__ __launch_bounds__(kMbThreads, HL_PIPE_WAVES_PER_EU) void k_pipeline(P
 #if !defined(HL_KERNELS_ONLY)  // (hl_encoder_fam3.hip compiles the kernels above again, with HL_FAM3=1)
 extern "C" hipError_t hl_fam3_launch_pipeline(const void* args, size_t psz, int mbw, int mbh, int workgroups, hipStream_t stream);
 extern "C" hipError_t hl_fam3_pipeline_occupancy(int* per_cu);
+// (hl_encoder_t256.hip: once more, with 256-lane workgroups)
+extern "C" hipError_t hl_t256_launch_pipeline(const void* args, size_t psz, int mbw, int mbh, int workgroups, hipStream_t stream);
+extern "C" hipError_t hl_t256_pipeline_occupancy(int* per_cu);
+
+// Pictures of a run (over all its streams) from which the launcher picks the
+// 256-lane build on its own; 0: never.  At 1920x1088 it loses 4 % on a run of
+// 20 pictures, ties at 30 and wins 8 % at 36, 16 % at 120 (DESIGN.md §9.4,
+// tools/run_length_sweep.py).
+constexpr int kT256MinPictures = 36;
+
+// The build of k_pipeline a run launches: 0 the one with the 8x8-family
+// helper tasks (hl_encoder_fam3.hip), 1 this file's 512-lane one, 2 the
+// 256-lane one (hl_encoder_t256.hip).  mode: hl_amd_set_pipeline_build.  A
+// run that qualifies for the helper tasks (fam3: a lone picture, unless they
+// are off) keeps their build -- only it has them; two macroblocks per CU pay
+// only while the run keeps twice the workgroups supplied with ready tasks,
+// which a short run does not.
+static int pipeline_build_choice(int mode, int pictures, bool fam3)
+{
+    if (mode < 0 || mode > 2 || pictures < 1) return -1;
+    if (fam3) return 0;
+    if (pictures == 1 || mode == 1) return 1;
+    if (mode == 2) return 2;
+    return kT256MinPictures > 0 && pictures >= kT256MinPictures ? 2 : 1;
+}
+
 static int diag_count(int mbw, int rows, int diag)
 {
     const int ylo = std::max(0, (diag - mbw + 2) / 2);
@@ -987,6 +1013,7 @@ struct hl_amd_encoder_s {
     int32_t helper_kept = 0, helper_rejected = 0, helper_self = 0;  // hl_amd_last_helper_stats
     int fam3 = 1;                                // ... and 8x8-family helper tasks (HL_AMD_FAM3: 0 off, 2 runs too)
     int memo = kMemoSlots;                       // FrameArgs::memo: slots of the candidate evaluation's memo (HL_AMD_MEMO: 0 off, N slots)
+    int pipe_build = 0, last_build = -1;         // hl_amd_set_pipeline_build (HL_AMD_T256), hl_amd_last_pipeline_build
     int32_t fam3_kept = 0, fam3_rejected = 0;    // hl_amd_last_fam3_stats
     Fam3Out* d_f3 = nullptr;                     // 8x8-family partitioning helper results [MB][4] ([slot][MB][4] with HL_AMD_FAM3=2)
     PipeFrame *d_pf, *h_pf;
@@ -1152,7 +1179,9 @@ extern "C" int32_t hl_amd_encoder_create(const hl_amd_params_t* p, hl_amd_encode
         e->fam3 = h3 ? atoi(h3) : 1;  // 0 off, 1 lone pictures, 2 runs of one stream too (their first / last pictures, HL_AMD_F3_EDGE)
         const char* hm = getenv("HL_AMD_MEMO");  // A/B knob: unset = the built capacity, 0 = off, N = N slots (a power of two)
         e->memo = hm ? atoi(hm) : kMemoSlots;
-        if (e->memo < 0 || e->memo > kMemoSlots || (e->memo & (e->memo - 1))) {
+        const char* ht = getenv("HL_AMD_T256");  // A/B knob (hl_amd_set_pipeline_build): 0 per run, 1 512-lane, 2 256-lane
+        e->pipe_build = ht ? atoi(ht) : 0;
+        if (e->pipe_build < 0 || e->pipe_build > 2 || e->memo < 0 || e->memo > kMemoSlots || (e->memo & (e->memo - 1))) {
             free_all(e);
             delete e;
             return HL_AMD_ERROR_INVALID_PARAMETER;
@@ -1590,6 +1619,8 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
     // a lone picture runs the kernel built with the 8x8-family helper tasks
     // (hl_encoder_fam3.hip): most workgroups would idle beside its wavefront
     const bool fam3 = e0->helpers && (slots == 1 ? e0->fam3 != 0 : S == 1 && e0->fam3 >= 2);
+    // ... and a long run the 256-lane build, two macroblocks per CU (hl_encoder_t256.hip)
+    const int build = pipeline_build_choice(e0->pipe_build, slots, fam3);
     for (int si = 0; si < S; ++si) {
         hl_amd_encoder_t* e = es[si];
         if (e->rc && (m != 1 || S != 1)) return HL_AMD_ERROR_INVALID_STATE;
@@ -1750,13 +1781,16 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
         int dev = 0, cus = 0, occ = 0;
         HL_HIP_CHECK(hipGetDevice(&dev));
         HL_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if (fam3) HL_HIP_CHECK(hl_fam3_pipeline_occupancy(&occ));  // the build that is launched
+        if (build == 0) HL_HIP_CHECK(hl_fam3_pipeline_occupancy(&occ));  // the build that is launched
+        else if (build == 2) HL_HIP_CHECK(hl_t256_pipeline_occupancy(&occ));
         else HL_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_pipeline, kMbThreads, 0));
         wgs = std::max(1, cus * occ);
     }
     if (e0->timing) HL_HIP_CHECK(hipEventRecord(e0->ev[4], e0->stream));
     for (int si = 0; si < S; ++si) es[si]->run_t0 = std::chrono::steady_clock::now();
-    if (fam3) HL_HIP_CHECK(hl_fam3_launch_pipeline(&P, sizeof(P), e0->mbw, e0->mbh, wgs, e0->stream));
+    for (int si = 0; si < S; ++si) es[si]->last_build = build;
+    if (build == 0) HL_HIP_CHECK(hl_fam3_launch_pipeline(&P, sizeof(P), e0->mbw, e0->mbh, wgs, e0->stream));
+    else if (build == 2) HL_HIP_CHECK(hl_t256_launch_pipeline(&P, sizeof(P), e0->mbw, e0->mbh, wgs, e0->stream));
     else k_pipeline<<<wgs, kMbThreads, 0, e0->stream>>>(P, e0->mbw, e0->mbh);
     HL_HIP_CHECK(hipGetLastError());
     if (e0->timing) HL_HIP_CHECK(hipEventRecord(e0->ev[5], e0->stream));
@@ -2125,6 +2159,22 @@ extern "C" int32_t hl_amd_set_pipeline(hl_amd_encoder_t* e, int32_t workgroups, 
     e->window = window;
     return HL_AMD_SUCCESS;
 }
+
+extern "C" int32_t hl_amd_set_pipeline_build(hl_amd_encoder_t* e, int32_t mode)
+{
+    if (!e || mode < 0 || mode > 2) return HL_AMD_ERROR_INVALID_PARAMETER;
+    e->pipe_build = mode;
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_last_pipeline_build(hl_amd_encoder_t* e) { return e ? e->last_build : -1; }
+
+extern "C" int32_t hl_amd_pipeline_build_choice(int32_t mode, int32_t pictures, int32_t fam3)
+{
+    return pipeline_build_choice(mode, pictures, fam3 != 0);
+}
+
+extern "C" int32_t hl_amd_pipeline_build_threshold(void) { return kT256MinPictures; }
 
 // Resident workgroups per CU of the pipelined kernel (HIP occupancy query).
 extern "C" int32_t hl_amd_pipeline_occupancy(void)

@@ -997,25 +997,33 @@ HD void mb_diag_inputs(Ctx& c)
 #endif
 }
 
-#if defined(__HIP_DEVICE_COMPILE__) && HL_MB_THREADS >= 512
+#if defined(__HIP_DEVICE_COMPILE__) && (HL_MB_THREADS >= 512 || HL_MB_THREADS == 256)
 // MB start on the device: every global load of the MB start is issued in one
 // round -- the MB objects of this address and of A, B, C, D (16-byte words),
 // the source samples, the intra neighbour samples of the current picture and
 // the CAVLC length tables -- and lands in LDS; the derivations then run from
 // LDS, each on its own lanes.  Same results as the host version below.
-// The lane assignment needs 512 lanes (smaller workgroups take the generic
-// strided version below).
-__device__ __forceinline__ void mb_begin(Ctx& c)
+// The lane assignment is a map of 512 lanes: a 256-lane workgroup takes two
+// of its lanes per lane (tid and tid + 256), the loads of both issued before
+// the first store (workgroups of any other size below 512 lanes take the
+// generic strided version below).  Each part takes its lane of the map as `tid`.
+constexpr int kBeginLanes = 512;
+constexpr int kBeginW = (int)(sizeof(MbState) / 16);  // 16-byte words per MB object
+static_assert(5 * kBeginW + 32 <= 448 && (kMbThreads >= kBeginLanes || 2 * kMbThreads == kBeginLanes), "mb_begin lane map");
+struct MbBeginLoads {  // what one lane of the map loads in round 1
+    uint4 q;
+    int b1, b2, b3, b4;
+    uint32_t b5;
+};
+
+// ---- round 1: loads (addresses clamped to valid memory, values unused there)
+__device__ __forceinline__ MbBeginLoads mb_begin_load(Ctx& c, const int tid)
 {
     const FrameArgs& F = c.F;
-    Shared& S = c.S;
-    const int tid = c.tid;
     const int a = c.addr;
     const int hasA = c.mbx > 0, hasB = c.mby > 0, hasC = c.mby > 0 && c.mbx < F.mbw - 1, hasD = c.mbx > 0 && c.mby > 0;
     const int xc = c.xL >> 1, yc = c.yL >> 1;
-    constexpr int kW = (int)(sizeof(MbState) / 16);  // 16-byte words per MB object
-    static_assert(5 * kW + 32 <= 448 && kMbThreads >= 464, "mb_begin lane map");
-    // ---- round 1: loads (addresses clamped to valid memory, values unused there)
+    constexpr int kW = kBeginW;
     uint4 q = make_uint4(0, 0, 0, 0);
     int b1 = kNA, b2 = 0, b3 = 0, b4 = 0;
     if (tid < 5 * kW) {
@@ -1054,7 +1062,18 @@ __device__ __forceinline__ void mb_begin(Ctx& c)
     if (tid >= 256) b4 = kRbTab.v[(tid - 256) >> 4][tid & 15];
     uint32_t b5 = 0;
     if (tid >= 240 && tid < 240 + 4 * 17) b5 = kTok3Tab.v[(tid - 240) / 17][(tid - 240) % 17];
-    // ---- stores
+    return MbBeginLoads{q, b1, b2, b3, b4, b5};
+}
+
+// ---- round 1: stores
+__device__ __forceinline__ void mb_begin_store(Ctx& c, const int tid, const MbBeginLoads& L)
+{
+    const FrameArgs& F = c.F;
+    Shared& S = c.S;
+    constexpr int kW = kBeginW;
+    const uint4 q = L.q;
+    const int b1 = L.b1, b2 = L.b2, b3 = L.b3, b4 = L.b4;
+    const uint32_t b5 = L.b5;
     if (tid < 5 * kW) reinterpret_cast<uint4*>(S.nbst)[tid] = q;
     else if (tid < 5 * kW + 16) reinterpret_cast<uint4*>(S.src)[tid - 5 * kW] = q;
     else if (tid < 5 * kW + 32) {
@@ -1069,9 +1088,7 @@ __device__ __forceinline__ void mb_begin(Ctx& c)
     if (tid < 3 * 4 * 17) S.ct.tok[tid / 68][(tid / 17) % 4][tid % 17] = (uint8_t)b3;
     if (tid >= 256) S.ct.rb[(tid - 256) >> 4][tid & 15] = (uint8_t)b4;
     if (tid >= 240 && tid < 240 + 4 * 17) S.ct.tok3[(tid - 240) / 17][(tid - 240) % 17] = b5;
-    if (tid >= kMbThreads - 48) (&S.be_tcm[0][0])[tid - (kMbThreads - 48)] = 0u;  // every slot empty at the MB start
-#pragma unroll
-    for (int t = tid; t < kMemoSlots; t += kMbThreads) S.memo[t].x = 0;  // the memo's keys: empty (never an epoch tag: a stale alias would be a silent wrong answer)
+    if (tid >= kBeginLanes - 48) (&S.be_tcm[0][0])[tid - (kBeginLanes - 48)] = 0u;  // every slot empty at the MB start
     if (tid >= 448 && tid < 464) {
         const int8_t* e = kQpelTab[tid - 448];
         const uint32_t q = (uint32_t)(e[0] | (e[1] << 2) | (e[2] << 3) | ((e[3] >= 0) << 4) | ((e[3] >= 0 ? e[3] : 0) << 5) | (e[4] << 7) | (e[5] << 8));
@@ -1079,8 +1096,14 @@ __device__ __forceinline__ void mb_begin(Ctx& c)
         const int o1 = (int)(q & 3) * F.plsz + (int)((q >> 3) & 1) * F.pstride + (int)((q >> 2) & 1);
         S.qoff[tid - 448] = make_int2(o1, (q & 16) ? (int)((q >> 5) & 3) * F.plsz + (int)((q >> 8) & 1) * F.pstride + (int)((q >> 7) & 1) : o1);
     }
-    HL_SYNC();
-    // ---- round 2: derivations from LDS, spread over the waves
+}
+
+// ---- round 2: derivations from LDS, spread over the waves
+__device__ __forceinline__ void mb_begin_derive(Ctx& c, const int tid)
+{
+    const FrameArgs& F = c.F;
+    Shared& S = c.S;
+    const int hasA = c.mbx > 0, hasB = c.mby > 0, hasC = c.mby > 0 && c.mbx < F.mbw - 1, hasD = c.mbx > 0 && c.mby > 0;
     // availability of MB w (no dynamically indexed array: it would live in scratch)
     auto av = [&](int w) -> bool { return w == 0 || (w == 1 ? hasA : (w == 2 ? hasB : (w == 3 ? hasC : hasD))); };
     if (tid < 30) {  // motion grid: row -1 from D / B / C, column -1 from A, inside undecided
@@ -1197,6 +1220,22 @@ __device__ __forceinline__ void mb_begin(Ctx& c)
             S.mb_type = 0;
         }
     }
+}
+
+__device__ __forceinline__ void mb_begin(Ctx& c)
+{
+    Shared& S = c.S;
+    constexpr int kR = kMbThreads >= kBeginLanes ? 1 : kBeginLanes / kMbThreads;  // lanes of the map per lane
+    MbBeginLoads L[kR];
+#pragma unroll
+    for (int r = 0; r < kR; ++r) L[r] = mb_begin_load(c, c.tid + r * kMbThreads);
+#pragma unroll
+    for (int r = 0; r < kR; ++r) mb_begin_store(c, c.tid + r * kMbThreads, L[r]);
+#pragma unroll
+    for (int t = c.tid; t < kMemoSlots; t += kMbThreads) S.memo[t].x = 0;  // the memo's keys: empty (never an epoch tag: a stale alias would be a silent wrong answer)
+    HL_SYNC();
+#pragma unroll
+    for (int r = 0; r < kR; ++r) mb_begin_derive(c, c.tid + r * kMbThreads);
     HL_SYNC();
     mb_diag_inputs(c);
 }

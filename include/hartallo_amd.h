@@ -243,6 +243,27 @@ int32_t hl_amd_set_pipeline(hl_amd_encoder_t* encoder, int32_t workgroups, int32
  * geometry tuning), or -1 */
 int32_t hl_amd_pipeline_occupancy(void);
 
+/* Which build of the pipelined kernel a run launches: 0 = chosen per run
+ * (the default), 1 = 512-lane workgroups (one macroblock per CU), 2 = 256-lane
+ * workgroups (two macroblocks per CU) for every run of more than one picture.
+ * A lone picture keeps the build with the 8x8-family helper tasks whatever
+ * the mode.  hl_amd_encode_streams follows its first encoder's mode.
+ * Results do not depend on it. */
+int32_t hl_amd_set_pipeline_build(hl_amd_encoder_t* encoder, int32_t mode);
+
+/* the build the last pipelined run launched: 0 = with the 8x8-family helper
+ * tasks (512 lanes), 1 = 512-lane, 2 = 256-lane; -1 before any run */
+int32_t hl_amd_last_pipeline_build(hl_amd_encoder_t* encoder);
+
+/* The launcher's choice (a pure function; no device): the build -- as
+ * hl_amd_last_pipeline_build reports it -- of a run that holds `pictures`
+ * pictures over all its streams, under `mode`, where `fam3` says that the run
+ * qualifies for the 8x8-family helper tasks.  -1 for an invalid argument. */
+int32_t hl_amd_pipeline_build_choice(int32_t mode, int32_t pictures, int32_t fam3);
+
+/* pictures of a run from which mode 0 picks the 256-lane build; 0 = never */
+int32_t hl_amd_pipeline_build_threshold(void);
+
 /* reconstructed (deblocked) picture of the last encoded frame, i.e. the
  * reference picture the next frame predicts from (dpb.c:160-170) */
 int32_t hl_amd_get_recon(hl_amd_encoder_t* encoder, uint8_t* y, uint8_t* u, uint8_t* v);

@@ -16,7 +16,7 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 def _disassemble_all(lib, td):
     """Every code object of the library's .hip_fatbin (one bundle per HIP
-    translation unit: hl_encoder.hip and hl_encoder_fam3.hip)."""
+    translation unit: hl_encoder.hip, hl_encoder_fam3.hip, hl_encoder_t256.hip)."""
     fat = os.path.join(td, "fat.bin")
     subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", lib], check=True, capture_output=True)
     data = open(fat, "rb").read()

@@ -20,7 +20,7 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 def resources(lib):
     """Every code object of the library's .hip_fatbin (one bundle per HIP
-    translation unit: hl_encoder.hip and hl_encoder_fam3.hip)."""
+    translation unit: hl_encoder.hip, hl_encoder_fam3.hip, hl_encoder_t256.hip)."""
     notes = ""
     with tempfile.TemporaryDirectory() as td:
         fat = os.path.join(td, "fat.bin")

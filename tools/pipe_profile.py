@@ -66,7 +66,7 @@ def main():
     print(f"wg,R,window={geo}: {n} P pictures in {dt * 1e3:.1f} ms (kernel {ms[1]:.1f} ms, reruns {enc.last_reruns()}) helpers {enc.last_helper_stats()}")
     life, wait, mb, filt, tasks = cnt[44], cnt[40], cnt[41], cnt[42], cnt[43]
     if life:
-        wgs = geo[0] or 256
+        wgs = geo[0] or (512 if enc.last_pipeline_build() == 2 else 256)  # (HL_AMD_T256=2: two workgroups per CU)
         print(f"   workgroups {wgs}, tasks {tasks} ({tasks / max(1, n * nmb):.2f} per MB), mean lifetime {life / wgs / 1e6:.1f} Mcycles"
               f" (~{life / wgs / (ms[1] * 1e-3) / 1e9:.2f} GHz shader clock if the kernel spans it)")
         hlp, hn = cnt[45], cnt[46]

@@ -41,7 +41,7 @@ def timed_launch(d):
     path = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)[0]
     acc = collections.defaultdict(lambda: collections.defaultdict(float))
     for r in csv.DictReader(open(path)):
-        if not r["Kernel_Name"].startswith("k_pipeline"):
+        if not r["Kernel_Name"].split("(")[0].endswith("k_pipeline"):  # (any build: hl_fam3::, hl_t256::)
             continue
         key = r.get("Dispatch_Id") or r.get("Correlation_Id") or r.get("Start_Timestamp")
         acc[int(key)][r["Counter_Name"]] += float(r["Counter_Value"])
