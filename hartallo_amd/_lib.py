@@ -86,6 +86,11 @@ EXPORTED_SYMBOLS = (
     "hl_amd_encode_aus_batch",
     "hl_amd_get_layer_input",
     "hl_amd_bench_pyramid",
+    "hl_amd_set_scenecut",
+    "hl_amd_scene_is_cut",
+    "hl_amd_last_scene_stats",
+    "hl_amd_debug_scene_mb",
+    "hl_amd_bench_scene",
     "hl_amd_version",
 )
 
@@ -300,6 +305,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         if hasattr(lib, name):  # (absent from builds before the layer pyramid loaded through HL_LIB)
             getattr(lib, name).argtypes = args
             getattr(lib, name).restype = i32
+    u64 = ctypes.c_uint64
+    for name, args in (("hl_amd_set_scenecut", [vp, i32, i32, i32]), ("hl_amd_scene_is_cut", [u64, u64, i32]),
+                       ("hl_amd_last_scene_stats", [vp, i32, ctypes.POINTER(u64)]),
+                       ("hl_amd_debug_scene_mb", [vp, i32, vp, vp, ctypes.c_size_t]),
+                       ("hl_amd_bench_scene", [vp, i32, ctypes.POINTER(ctypes.c_float)])):
+        if hasattr(lib, name):  # (absent from builds before scene-cut detection loaded through HL_LIB)
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = i32
     lib.hl_amd_svc_layer_ms.argtypes = [vp]
     lib.hl_amd_svc_layer_ms.restype = ctypes.c_float
     lib.hl_amd_version.argtypes = []
@@ -476,6 +489,47 @@ class Encoder:
     def last_qp(self) -> int:
         """SliceQPY of the last encoded picture."""
         return self.lib.hl_amd_last_qp(self._h)
+
+    def set_scenecut(self, threshold: int, min_gap: int = 1, range: int = 8) -> None:
+        """Scene-cut detection (hl_amd_set_scenecut): every input frame is
+        compared with the one before it on the GPU, and a cut -- 256 P >=
+        threshold I, at least min_gap pictures after the last IDR, encoding
+        AUTO -- is coded as if the caller had forced an IDR.  threshold 0: off
+        (the default); range: the search range in samples, 0..16."""
+        rc = self.lib.hl_amd_set_scenecut(self._h, threshold, min_gap, range)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_set_scenecut")
+
+    def last_scene_stats(self, k: int) -> dict:
+        """Picture k of the last encode call (hl_amd_last_scene_stats): P, I,
+        whether it was analysed and whether the detector turned it into an
+        IDR."""
+        a = (ctypes.c_uint64 * 4)()
+        rc = self.lib.hl_amd_last_scene_stats(self._h, k, a)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_last_scene_stats")
+        return {"P": int(a[0]), "I": int(a[1]), "analysed": bool(a[2]), "turned": bool(a[3])}
+
+    def debug_scene_mb(self, k: int):
+        """(inter, intra) of every macroblock of picture k of the last encode
+        call, uint32 arrays of shape (mbh, mbw) (hl_amd_debug_scene_mb)."""
+        import numpy as np
+
+        mbh, mbw = self.height // 16, self.width // 16
+        inter, intra = np.zeros((mbh, mbw), np.uint32), np.zeros((mbh, mbw), np.uint32)
+        rc = self.lib.hl_amd_debug_scene_mb(self._h, k, inter.ctypes.data, intra.ctypes.data, mbh * mbw)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_debug_scene_mb")
+        return inter, intra
+
+    def bench_scene(self, iters: int = 50) -> float:
+        """average ms of the scene analysis launch of the last encode call,
+        whose frames must still be there (diagnostics)"""
+        ms = ctypes.c_float()
+        rc = self.lib.hl_amd_bench_scene(self._h, iters, ctypes.byref(ms))
+        if rc:
+            raise HlAmdError(rc, "hl_amd_bench_scene")
+        return ms.value
 
     def bench_planes(self, iters: int = 50) -> float:
         """average ms per launch of the quarter-pel plane kernel (diagnostics)"""

@@ -36,6 +36,7 @@
 #include "hl_svc.h"
 #include "hl_cavlc.h"
 #include "hl_pyramid.h"
+#include "hl_scene.h"
 #include "hl_writer.h"
 #endif
 
@@ -969,6 +970,9 @@ static PicPlan plan_picture(hl_amd_params_t& live, int32_t& gop_left, const hl_a
     return PicPlan{intra, std::min(64, std::max(1, live.me_range)) /* rdo.c:847 */, live.deblock != 0, live.me_early_term != 0};
 }
 
+// pictures coded since the last IDR, after one more (1 right after an IDR): the scene-cut planner's gap
+static int32_t next_since_idr(int32_t since, bool idr) { return idr ? 1 : since < INT32_MAX ? since + 1 : since; }
+
 struct hl_amd_encoder_s {
     hl_amd_params_t p;  // me_range, deblock, me_early_term, gop_size: the live values (the last ctl's)
     int W, H, Wc, Hc, mbw, mbh, nmb, qpc, pstride;
@@ -1057,6 +1061,24 @@ struct hl_amd_encoder_s {
     std::vector<LaOut> la_out;                   // coded results not yet handed out, from la_head
     size_t la_head = 0;
     LaOut la_cur;                                // the result the last call handed out (valid until the next call)
+    // scene-cut detection (hl_amd_set_scenecut, hl_scene.h): the input frames
+    // of a call are analysed in one launch before the call is planned; a cut
+    // becomes HL_AMD_ENCODING_INTRA in the call's effective ctl
+    int32_t sc_thr = 0, sc_gap = 1, sc_range = 8;  // sc_thr 0: off
+    int32_t since_idr = 0;                       // pictures coded since the last IDR (1 right after one); moves with gop_left
+    uint8_t* d_sc_prev = nullptr;                // two luma frames: the last committed frame's ([sc_cur]), the call's under way
+    int sc_cur = 0;
+    bool sc_have_prev = false;                   // d_sc_prev[sc_cur] holds a frame
+    const uint8_t** d_sc_tab = nullptr;          // [sc_cap] luma planes of the call's frames
+    uint32_t* d_sc_mb = nullptr;                 // [sc_cap][MB][2] inter, intra
+    unsigned long long* d_sc_sums = nullptr;     // [sc_cap][2] P, I
+    unsigned long long* h_sc_sums = nullptr;     // ... read back (pinned)
+    int sc_cap = 0;
+    int sc_n = 0;                                // frames of the last call's analysis (0: none)
+    const uint8_t* sc_prev0 = nullptr;           // ... and the frame its first was compared with (bench)
+    std::vector<uint64_t> sc_P, sc_I;            // per frame of the last call (hl_amd_last_scene_stats)
+    std::vector<char> sc_analysed, sc_turned;
+    std::vector<hl_amd_frame_ctl_t> sc_ctl;      // the last call's effective ctl
 };
 
 static void svc_free(hl_amd_encoder_t* e);
@@ -1080,6 +1102,11 @@ static void free_all(hl_amd_encoder_t* e)
     (void)hipFree(e->d_prof);
     (void)hipFree(e->d_rows);
     (void)hipFree(e->d_la);
+    (void)hipFree(e->d_sc_prev);
+    (void)hipFree(e->d_sc_tab);
+    (void)hipFree(e->d_sc_mb);
+    (void)hipFree(e->d_sc_sums);
+    (void)hipHostFree(e->h_sc_sums);
     (void)hipFree(e->d_bpic);
     (void)hipFree(e->d_bpl);
     (void)hipFree(e->d_brec);
@@ -1382,6 +1409,7 @@ static int32_t encode_frame(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t
     ++e->pict_count;
     if (intra) ++e->idr_pic_id;
     --e->gop_left;
+    e->since_idr = next_since_idr(e->since_idr, intra);
     ++e->frame_index;
     return HL_AMD_SUCCESS;
 }
@@ -1950,6 +1978,7 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
             ++e->pict_count;
             if (e->run_plan[k].intra) ++e->idr_pic_id;
             --e->gop_left;
+            e->since_idr = next_since_idr(e->since_idr, e->run_plan[k].intra != 0);
             ++e->frame_index;
         }
         e->chain_end = carry;
@@ -2001,6 +2030,122 @@ static void begin_call(hl_amd_encoder_t* e, int n)
     e->fam3_kept = e->fam3_rejected = 0;
 }
 
+// ---------------------------------------------------------------------------
+// Scene-cut detection (hl_amd_set_scenecut; no reference interface: the
+// reference's picture types come from gop_size and hl_frame_t.encoding alone).
+// k_scene (hl_scene.h) compares every input frame of a call with the input
+// frame before it -- one launch per call and encoder on the encoder's stream,
+// before anything is planned -- and a cut becomes HL_AMD_ENCODING_INTRA in the
+// call's effective ctl: plan_picture and everything behind it see a caller
+// who forced that IDR.
+// ---------------------------------------------------------------------------
+static int32_t scene_is_cut(uint64_t P, uint64_t I, int32_t thr)
+{
+    if (thr < 1 || thr > 256) return -1;
+    // 256 P >= thr I in 128 bits (P <= I by construction, but any pair is taken)
+    return I > 0 && (unsigned __int128)P * 256u >= (unsigned __int128)I * (unsigned)thr ? 1 : 0;
+}
+
+static hipError_t ensure_scene(hl_amd_encoder_t* e, int n)
+{
+    if (n <= e->sc_cap) return hipSuccess;
+    (void)hipFree(e->d_sc_tab);
+    (void)hipFree(e->d_sc_mb);
+    (void)hipFree(e->d_sc_sums);
+    (void)hipHostFree(e->h_sc_sums);
+    e->d_sc_tab = nullptr;
+    e->d_sc_mb = nullptr;
+    e->d_sc_sums = e->h_sc_sums = nullptr;
+    e->sc_cap = 0;
+    e->sc_n = 0;
+    hipError_t err = hipMalloc(&e->d_sc_tab, sizeof(uint8_t*) * n);
+    if (err == hipSuccess) err = hipMalloc(&e->d_sc_mb, sizeof(uint32_t) * 2 * e->nmb * n);
+    if (err == hipSuccess) err = hipMalloc(&e->d_sc_sums, sizeof(unsigned long long) * 2 * n);
+    if (err == hipSuccess) err = hipHostMalloc(&e->h_sc_sums, sizeof(unsigned long long) * 2 * n, hipHostMallocDefault);
+    if (err == hipSuccess) e->sc_cap = n;
+    return err;
+}
+
+// the analysis launch(es) of a call's n frames (grid z holds 65535 frames)
+static hipError_t launch_scene_call(hl_amd_encoder_t* e, int n, const uint8_t* prev0)
+{
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        hl::SceneArgs A{};
+        A.tab = e->d_sc_tab;
+        A.prev0 = prev0;
+        A.mb = e->d_sc_mb + (size_t)2 * e->nmb * f0;
+        A.sums = e->d_sc_sums + (size_t)2 * f0;
+        A.W = e->W;
+        A.H = e->H;
+        A.R = e->sc_range;
+        A.f0 = f0;
+        const hipError_t err = hl::launch_scene(A, std::min(65535, n - f0), e->stream);
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+// The call's n frames (device luma planes y, the call's ctl or null) analysed
+// and planned: *eff = the ctl the call is coded with -- the caller's, or a
+// copy with INTRA at the frames the detector turns (the other four fields as
+// they would have been: with a null ctl the live values).  Nothing of the
+// encoder's state moves: scene_commit does that once the call has.
+static int32_t scene_plan(hl_amd_encoder_t* e, int n, const uint8_t* const* y, const hl_amd_frame_ctl_t* ctl, const hl_amd_frame_ctl_t** eff)
+{
+    *eff = ctl;
+    e->sc_n = 0;
+    if (!e->sc_thr) return HL_AMD_SUCCESS;
+    for (int i = 0; i < n; ++i)
+        if ((uintptr_t)y[i] & 3) return HL_AMD_ERROR_INVALID_PARAMETER;  // k_scene loads 4-byte words
+    HL_HIP_CHECK(ensure_scene(e, n));
+    const size_t ny = (size_t)e->W * e->H;
+    uint8_t* const carry[2] = {e->d_sc_prev, e->d_sc_prev + ny};
+    const uint8_t* prev0 = e->sc_have_prev ? carry[e->sc_cur] : nullptr;
+    HL_HIP_CHECK(hipMemcpyAsync(e->d_sc_tab, y, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, e->stream));
+    HL_HIP_CHECK(hipMemsetAsync(e->d_sc_sums, 0, sizeof(unsigned long long) * 2 * n, e->stream));
+    if (n > 1 || prev0) HL_HIP_CHECK(launch_scene_call(e, n, prev0));
+    // the call's last frame is the next call's previous one, once this call commits
+    HL_HIP_CHECK(hipMemcpyAsync(carry[e->sc_cur ^ 1], y[n - 1], ny, hipMemcpyDeviceToDevice, e->stream));
+    HL_HIP_CHECK(hipMemcpyAsync(e->h_sc_sums, e->d_sc_sums, sizeof(unsigned long long) * 2 * n, hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipStreamSynchronize(e->stream));  // (the caller's table may go once this call returns, too)
+    e->sc_P.resize(n);
+    e->sc_I.resize(n);
+    e->sc_analysed.resize(n);
+    e->sc_turned.resize(n);
+    e->sc_ctl.resize(n);
+    hl_amd_params_t live = e->p;
+    int32_t gl = e->gop_left, since = e->since_idr;
+    bool any = false;
+    for (int k = 0; k < n; ++k) {
+        e->sc_analysed[k] = k > 0 || prev0 != nullptr;
+        e->sc_P[k] = e->sc_analysed[k] ? e->h_sc_sums[2 * k] : 0;
+        e->sc_I[k] = e->sc_analysed[k] ? e->h_sc_sums[2 * k + 1] : 0;
+        hl_amd_frame_ctl_t c = ctl ? ctl[k] : hl_amd_frame_ctl_t{HL_AMD_ENCODING_AUTO, live.me_range, live.deblock, live.me_early_term, live.gop_size};
+        e->sc_turned[k] = e->sc_analysed[k] && scene_is_cut(e->sc_P[k], e->sc_I[k], e->sc_thr) == 1 && since >= e->sc_gap &&
+                          c.encoding == HL_AMD_ENCODING_AUTO;
+        if (e->sc_turned[k]) {
+            c.encoding = HL_AMD_ENCODING_INTRA;
+            any = true;
+        }
+        e->sc_ctl[k] = c;
+        const PicPlan plan = plan_picture(live, gl, &c);  // (on copies: what the call's commit will do)
+        --gl;
+        since = next_since_idr(since, plan.intra != 0);
+    }
+    e->sc_n = n;
+    e->sc_prev0 = prev0;
+    if (any) *eff = e->sc_ctl.data();
+    return HL_AMD_SUCCESS;
+}
+
+// the call committed: its last frame is the stream's previous input frame
+static void scene_commit(hl_amd_encoder_t* e)
+{
+    if (!e->sc_thr || !e->sc_n) return;
+    e->sc_cur ^= 1;
+    e->sc_have_prev = true;
+}
+
 // n consecutive pictures of the stream, every one through a pipelined run:
 // runs span GOPs (IDR pictures included), kMaxRun bounds the run's buffers
 // (~22 MB of HBM and 9 MB of pinned host memory per 1088p picture); under
@@ -2010,6 +2155,10 @@ static int32_t encode_pictures(hl_amd_encoder_t* e, int n, const uint8_t* const*
                                hl_amd_result_t* results, const hl_amd_frame_ctl_t* ctl = nullptr)
 {
     if (e->broken) return HL_AMD_ERROR_INVALID_STATE;
+    {  // scene cuts of the whole call, before its first run (one launch, however the call is split below)
+        const int32_t rc = scene_plan(e, n, y, ctl, &ctl);
+        if (rc) return rc;
+    }
     begin_call(e, n);
     for (int i = 0; i < n;) {
         const int m = e->rc ? 1 : std::min(n - i, kMaxRun);
@@ -2017,6 +2166,7 @@ static int32_t encode_pictures(hl_amd_encoder_t* e, int n, const uint8_t* const*
         if (rc) return rc;
         i += m;
     }
+    scene_commit(e);
     return HL_AMD_SUCCESS;
 }
 
@@ -2045,6 +2195,13 @@ extern "C" int32_t hl_amd_encode_streams_ex(hl_amd_encoder_t* const* encoders, i
         const int32_t rc = check_ctl(encoders[s], ctl + (size_t)s * n, n);
         if (rc) return rc;
     }
+    // scene cuts: every encoder has its own setting and state, and its own
+    // launch on its own stream (a stream with the feature off launches nothing)
+    std::vector<const hl_amd_frame_ctl_t*> E(count, nullptr);
+    for (int s = 0; s < count; ++s) {
+        const int32_t rc = scene_plan(encoders[s], n, y + (size_t)s * n, ctl ? ctl + (size_t)s * n : nullptr, &E[s]);
+        if (rc) return rc;
+    }
     for (int s = 0; s < count; ++s) begin_call(encoders[s], n);
     std::vector<const uint8_t* const*> Y(count), U(count), V(count);
     std::vector<hl_amd_result_t*> R(count);
@@ -2056,12 +2213,13 @@ extern "C" int32_t hl_amd_encode_streams_ex(hl_amd_encoder_t* const* encoders, i
             U[s] = u + (size_t)s * n + i;
             V[s] = v + (size_t)s * n + i;
             R[s] = results + (size_t)s * n + i;
-            if (ctl) C[s] = ctl + (size_t)s * n + i;
+            if (E[s]) C[s] = E[s] + i;
         }
         const int32_t rc = encode_group(encoders, count, m, Y.data(), U.data(), V.data(), R.data(), i, C.data());
         if (rc) return rc;
         i += m;
     }
+    for (int s = 0; s < count; ++s) scene_commit(encoders[s]);
     return HL_AMD_SUCCESS;
 }
 
@@ -2269,6 +2427,78 @@ extern "C" int32_t hl_amd_set_lookahead(hl_amd_encoder_t* e, int32_t frames)
     (void)hipFree(e->d_la);
     e->d_la = nullptr;
     e->lookahead = frames;
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_set_scenecut(hl_amd_encoder_t* e, int32_t threshold, int32_t min_gap, int32_t range)
+{
+    if (!e || threshold < 0 || threshold > 256 || min_gap < 1 || range < 0 || range > hl::kScMaxR) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->svc) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // layers take no forced types
+    if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;   // queued frames come first (hl_amd_flush)
+    if (threshold && !e->d_sc_prev) {  // the carried-over luma, allocated when the feature is first enabled
+        if (hipMalloc(&e->d_sc_prev, (size_t)2 * e->W * e->H) != hipSuccess) {
+            e->d_sc_prev = nullptr;
+            return HL_AMD_ERROR_OUTOFMEMMORY;
+        }
+    }
+    if (!threshold || !e->sc_thr) e->sc_have_prev = false;  // off, or newly on: the next frame has no previous input frame
+    e->sc_thr = threshold;
+    e->sc_gap = min_gap;
+    e->sc_range = range;
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_scene_is_cut(uint64_t P, uint64_t I, int32_t threshold) { return scene_is_cut(P, I, threshold); }
+
+extern "C" int32_t hl_amd_last_scene_stats(hl_amd_encoder_t* e, int32_t k, uint64_t out4[4])
+{
+    if (!e || !out4) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->sc_n) return HL_AMD_ERROR_INVALID_STATE;  // the last call was not analysed
+    if (k < 0 || k >= e->sc_n) return HL_AMD_ERROR_INVALID_PARAMETER;
+    out4[0] = e->sc_P[k];
+    out4[1] = e->sc_I[k];
+    out4[2] = e->sc_analysed[k] ? 1 : 0;
+    out4[3] = e->sc_turned[k] ? 1 : 0;
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_debug_scene_mb(hl_amd_encoder_t* e, int32_t k, uint32_t* inter, uint32_t* intra, size_t mbs)
+{
+    if (!e || !inter || !intra) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->sc_n) return HL_AMD_ERROR_INVALID_STATE;
+    if (k < 0 || k >= e->sc_n || mbs != (size_t)e->nmb) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->sc_analysed[k]) return HL_AMD_ERROR_INVALID_STATE;  // no previous input frame: nothing was computed
+    std::vector<uint32_t> both((size_t)2 * e->nmb);
+    HL_HIP_CHECK(hipMemcpyAsync(both.data(), e->d_sc_mb + (size_t)2 * e->nmb * k, sizeof(uint32_t) * both.size(), hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipStreamSynchronize(e->stream));
+    for (int a = 0; a < e->nmb; ++a) {
+        inter[a] = both[2 * a];
+        intra[a] = both[2 * a + 1];
+    }
+    return HL_AMD_SUCCESS;
+}
+
+// k_scene alone: `iters` times the analysis launch of the last encode call
+// (the same frames into the same arrays; the caller's planes of that call must
+// still be there), timed with HIP events on the encoder's stream; *ms =
+// average milliseconds per launch.  Diagnostics, like hl_amd_bench_pyramid.
+extern "C" int32_t hl_amd_bench_scene(hl_amd_encoder_t* e, int32_t iters, float* ms)
+{
+    if (!e || iters <= 0 || !ms) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->sc_thr || !e->sc_n || (e->sc_n == 1 && !e->sc_prev0)) return HL_AMD_ERROR_INVALID_STATE;  // no launch to repeat
+    hipEvent_t a, b;
+    HL_HIP_CHECK(hipEventCreate(&a));
+    HL_HIP_CHECK(hipEventCreate(&b));
+    HL_HIP_CHECK(launch_scene_call(e, e->sc_n, e->sc_prev0));  // warm
+    HL_HIP_CHECK(hipEventRecord(a, e->stream));
+    for (int i = 0; i < iters; ++i) HL_HIP_CHECK(launch_scene_call(e, e->sc_n, e->sc_prev0));
+    HL_HIP_CHECK(hipEventRecord(b, e->stream));
+    HL_HIP_CHECK(hipEventSynchronize(b));
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, a, b);
+    *ms = t / iters;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
     return HL_AMD_SUCCESS;
 }
 
@@ -2818,6 +3048,8 @@ extern "C" int32_t hl_amd_add_layer(hl_amd_encoder_t* e, int32_t width, int32_t 
     if (!e || width <= 0 || height <= 0) return HL_AMD_ERROR_INVALID_PARAMETER;
     if (e->frame_index > 0 || e->la_n || (e->svc && e->svc->started)) return HL_AMD_ERROR_INVALID_STATE;
     e->lookahead = 1;  // (the look-ahead is AVC only: an encoder with layers ignores it)
+    e->sc_thr = 0;     // (scene-cut detection too: layers take no forced types)
+    e->sc_have_prev = false;
     if (!e->svc) e->svc = new SvcState();
     SvcState* s = e->svc;
     if ((int)s->w.size() >= 4) return HL_AMD_ERROR_OUTOFCAPACITY;  // HL_ENCODER_MAX_LAYERS

@@ -458,6 +458,55 @@ int32_t hl_amd_get_layer_input(hl_amd_encoder_t* encoder, int32_t layer, uint8_t
  * interface. */
 int32_t hl_amd_bench_pyramid(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
 
+/* Scene-cut detection.  No reference interface: the reference's picture types
+ * come from gop_size and hl_frame_t.encoding alone, and nothing there looks
+ * at the pictures.  With threshold 1..256 every input frame of an encode call
+ * is compared on the GPU with the input frame before it (k_scene: per 16x16
+ * luma macroblock intra = sum |p - mean| and inter = the smallest SAD over the
+ * displacements of [-range, range]^2 that stay inside the picture; per frame
+ * P = sum min(inter, intra), I = sum intra), and a frame with
+ * hl_amd_scene_is_cut(P, I, threshold), at least min_gap pictures after the
+ * last IDR of any cause and with encoding AUTO (or no ctl) is coded exactly as
+ * if the caller had passed HL_AMD_ENCODING_INTRA for it: the stream is the
+ * reference's for those hl_frame_t.encoding values.  HL_AMD_ENCODING_INTER is
+ * the caller's veto.  The first frame of a stream, and the first after the
+ * feature is switched on, have no previous frame and are never cuts.  Honoured
+ * by hl_amd_encode, _device, _batch, _streams (every encoder its own setting
+ * and state), their _ex forms and the look-ahead queue (analysed when the
+ * queue is coded).  A refused or failed call leaves the detector's state as
+ * it was.  With the feature on, device planes must be 4-byte aligned
+ * (HL_AMD_ERROR_INVALID_PARAMETER).
+ * threshold 0: off (the default; nothing is launched or allocated).
+ * min_gap >= 1, range 0..16, threshold 0..256, else
+ * HL_AMD_ERROR_INVALID_PARAMETER.  Between any two encode calls; while
+ * look-ahead frames are queued HL_AMD_ERROR_INVALID_STATE; on an encoder with
+ * layers HL_AMD_ERROR_NOT_IMPLEMENTED (layers take no forced types; adding a
+ * layer switches the feature off). */
+int32_t hl_amd_set_scenecut(hl_amd_encoder_t* encoder, int32_t threshold, int32_t min_gap, int32_t range);
+
+/* The detector's rule, a pure function (no device): 1 when I > 0 and
+ * 256 P >= threshold I, else 0; -1 for a threshold outside 1..256.  No
+ * reference interface (the rule is this project's). */
+int32_t hl_amd_scene_is_cut(uint64_t P, uint64_t I, int32_t threshold);
+
+/* Picture k of the last encode call (with look-ahead: the call that coded the
+ * queue): out4 = P, I, 1 if the picture was analysed, 1 if the detector turned
+ * it into an IDR.  HL_AMD_ERROR_INVALID_STATE when that call ran with the
+ * feature off.  No reference interface (nothing there to report). */
+int32_t hl_amd_last_scene_stats(hl_amd_encoder_t* encoder, int32_t k, uint64_t out4[4]);
+
+/* Diagnostics: inter and intra of every macroblock (mbs = the picture's
+ * macroblock count) of picture k of the last encode call;
+ * HL_AMD_ERROR_INVALID_STATE for a picture that was not analysed.  No
+ * reference interface (the tests' handle on k_scene). */
+int32_t hl_amd_debug_scene_mb(hl_amd_encoder_t* encoder, int32_t k, uint32_t* inter, uint32_t* intra, size_t mbs);
+
+/* Diagnostics: `iters` times the analysis launch of the last encode call (the
+ * same frames, which must still be there, into the same arrays); *ms = average
+ * ms per launch.  HL_AMD_ERROR_INVALID_STATE without such a launch.  No
+ * reference interface (like hl_amd_bench_pyramid). */
+int32_t hl_amd_bench_scene(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
+
 /* device time (ms) of the enhancement layers of the last access unit (with
  * hl_amd_set_timing on) */
 float hl_amd_svc_layer_ms(hl_amd_encoder_t* encoder);

@@ -93,6 +93,36 @@ static HL_ERROR_T gfx950_open(hl_codec_264_gfx950_t* self, hl_codec_t* base, hl_
         const char* la = getenv("HL_AMD_LOOKAHEAD");
         if (la && atoi(la) > 1 && (err = hl_amd_set_lookahead(self->enc, atoi(la)))) return (HL_ERROR_T)err;
     }
+    /* scene-cut detection (opt-in, no reference counterpart):
+     * HL_AMD_SCENECUT=threshold[:min_gap[:range]] (hl_amd_set_scenecut; 0 =
+     * off).  A frame the detector finds to be a cut is coded as if its
+     * hl_frame_t.encoding were INTRA.  A malformed value fails the open.  AVC
+     * only: adding a layer switches it off. */
+    {
+        const char* sc = getenv("HL_AMD_SCENECUT");
+        if (sc) {
+            long v[3] = {0, 1, 8}; /* min_gap and range: the defaults */
+            int i = 0, bad = 0;
+            const char* s = sc;
+            while (!bad) {
+                char* end = NULL;
+                if (i == 3 || *s < '0' || *s > '9') bad = 1;
+                else {
+                    v[i] = strtol(s, &end, 10);
+                    if (v[i] > 65536 || (*end && *end != ':')) bad = 1;
+                    ++i;
+                    if (!*end) break;
+                    s = end + 1;
+                }
+            }
+            if (!bad && (err = hl_amd_set_scenecut(self->enc, (int32_t)v[0], (int32_t)v[1], (int32_t)v[2])) == HL_AMD_ERROR_INVALID_PARAMETER) bad = 1;
+            if (bad) {
+                fprintf(stderr, "hl_codec_264_gfx950: HL_AMD_SCENECUT=\"%s\" is not threshold[:min_gap[:range]] (0..256, >= 1, 0..16)\n", sc);
+                return HL_ERROR_INVALID_PARAMETER;
+            }
+            if (err) return (HL_ERROR_T)err;
+        }
+    }
     /* SPS max_num_ref_frames / PPS num_ref_idx_l0_default_active_minus1
      * (hl_codec_264_sps.c:620-636, hl_codec_264_pps.c:291) */
     if ((err = hl_amd_set_max_ref_frame(self->enc, base->max_ref_frame))) return (HL_ERROR_T)err;
