@@ -3,6 +3,7 @@
 #   tests/emu/libhl_emu.so           test-only host build of the kernel logic
 #   tests/emu/libhl_pyr_emu.so       test-only host build of the layer pyramid (hl_pyramid.h)
 #   tests/emu/libhl_scene_emu.so     test-only host build of the scene-cut analysis (hl_scene.h)
+#   tests/emu/libhl_quality_emu.so   test-only host build of the quality metric (hl_quality.h)
 #   tests/emu/libhl_rec_emu.so       test-only host exports of the candidate record's pack / unpack (hl_mbcore.h)
 #   tests/gpu_unit/libhl_unit.so     test-only GPU unit kernels (coop pipeline vs scalar primitives)
 #   tests/gpu_unit/libhl_unit_cand.so  test-only GPU unit kernel (the search's candidate slot)
@@ -28,7 +29,7 @@ DEVFLAGS := -mllvm -amdgpu-sched-strategy=iterative-ilp
 all: product emu unit oracle sanitize
 
 product: hartallo_amd/libhartallo_amd.so
-emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_rec_emu.so
+emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_rec_emu.so
 unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so
 
 hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
@@ -49,6 +50,10 @@ tests/emu/libhl_pyr_emu.so: tests/emu/hl_pyr_emu.cpp $(CSRC)/hl_pyramid.h
 # the scene-cut analysis' staging and per-macroblock code on the host (no device code)
 tests/emu/libhl_scene_emu.so: tests/emu/hl_scene_emu.cpp $(CSRC)/hl_scene.h
 	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_scene_emu.cpp
+
+# the quality metric's staging, per-strip and per-window code on the host (no device code)
+tests/emu/libhl_quality_emu.so: tests/emu/hl_quality_emu.cpp $(CSRC)/hl_quality.h
+	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_quality_emu.cpp
 
 # the candidate record's pack and unpack functions on the host (no device code)
 tests/emu/libhl_rec_emu.so: tests/emu/hl_rec_emu.hip $(HDRS)
@@ -127,5 +132,5 @@ oracle: product  # oracle/_ref/drop_in_enc links the product library
 	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
-	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_rec_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
+	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_rec_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
 	$(MAKE) -C oracle clean

@@ -6,7 +6,7 @@ with the reference encoder, behind a
 C ABI (include/hartallo_amd.h) that a hartallo plugin forwards to.
 """
 from ._lib import (EXPORTED_SYMBOLS, HL_AMD_RESULT_TYPE_DATA, HL_AMD_RESULT_TYPE_HDR, LIB_PATH, EncodeResult, Encoder,
-                   FrameCtl, HlAmdError, SvcEncoder, load_library)
+                   FrameCtl, HlAmdError, Quality, SvcEncoder, load_library, psnr_db, ssim_mean)
 
 __all__ = [
     "Encoder",
@@ -15,6 +15,9 @@ __all__ = [
     "FrameCtl",
     "HlAmdError",
     "load_library",
+    "Quality",
+    "psnr_db",
+    "ssim_mean",
     "LIB_PATH",
     "EXPORTED_SYMBOLS",
     "HL_AMD_RESULT_TYPE_DATA",

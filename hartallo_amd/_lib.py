@@ -91,6 +91,12 @@ EXPORTED_SYMBOLS = (
     "hl_amd_last_scene_stats",
     "hl_amd_debug_scene_mb",
     "hl_amd_bench_scene",
+    "hl_amd_set_quality",
+    "hl_amd_last_quality",
+    "hl_amd_debug_quality_mb",
+    "hl_amd_bench_quality",
+    "hl_amd_psnr_db",
+    "hl_amd_ssim_mean",
     "hl_amd_version",
 )
 
@@ -194,6 +200,22 @@ def code_sha256(path: str) -> str:
         o, sz = by.get(sec, (0, 0))
         h.update(data[o:o + sz])
     return h.hexdigest()
+
+
+class Quality(ctypes.Structure):
+    """hl_amd_quality_t"""
+    _fields_ = [("sse", ctypes.c_uint64 * 3), ("samples", ctypes.c_uint64 * 3), ("ssim_q30", ctypes.c_int64 * 3),
+                ("windows", ctypes.c_uint64 * 3)]
+
+
+def psnr_db(sse: int, samples: int) -> float:
+    """10 log10(255^2 samples / sse); inf for sse = 0 (hl_amd_psnr_db)."""
+    return load_library().hl_amd_psnr_db(sse, samples)
+
+
+def ssim_mean(q30: int, windows: int) -> float:
+    """q30 / 2^30 / windows (hl_amd_ssim_mean)."""
+    return load_library().hl_amd_ssim_mean(q30, windows)
 
 
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
@@ -313,6 +335,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         if hasattr(lib, name):  # (absent from builds before scene-cut detection loaded through HL_LIB)
             getattr(lib, name).argtypes = args
             getattr(lib, name).restype = i32
+    for name, args in (("hl_amd_set_quality", [vp, i32]), ("hl_amd_last_quality", [vp, i32, i32, ctypes.POINTER(Quality)]),
+                       ("hl_amd_debug_quality_mb", [vp, i32, i32, vp, ctypes.c_size_t]),
+                       ("hl_amd_bench_quality", [vp, i32, ctypes.POINTER(ctypes.c_float)])):
+        if hasattr(lib, name):  # (absent from builds before the quality metric loaded through HL_LIB)
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = i32
+    for name, args in (("hl_amd_psnr_db", [u64, u64]), ("hl_amd_ssim_mean", [ctypes.c_int64, u64])):
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = ctypes.c_double
     lib.hl_amd_svc_layer_ms.argtypes = [vp]
     lib.hl_amd_svc_layer_ms.restype = ctypes.c_float
     lib.hl_amd_version.argtypes = []
@@ -529,6 +561,49 @@ class Encoder:
         rc = self.lib.hl_amd_bench_scene(self._h, iters, ctypes.byref(ms))
         if rc:
             raise HlAmdError(rc, "hl_amd_bench_scene")
+        return ms.value
+
+    def set_quality(self, on: bool = True) -> None:
+        """Per-picture quality (hl_amd_set_quality): every coded picture is
+        compared on the GPU with the planes it was coded from.  Off by
+        default; it changes no byte of the stream."""
+        rc = self.lib.hl_amd_set_quality(self._h, 1 if on else 0)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_set_quality")
+
+    def last_quality(self, k: int, layer: int = 0) -> dict:
+        """Picture k (of layer `layer`) of the last encode call
+        (hl_amd_last_quality): the integers sse, samples, ssim_q30, windows as
+        lists over Y, U, V, plus psnr_y/u/v (dB) and ssim_y/u/v."""
+        q = Quality()
+        rc = self.lib.hl_amd_last_quality(self._h, layer, k, ctypes.byref(q))
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_last_quality")
+        out = {f: [int(x) for x in getattr(q, f)] for f in ("sse", "samples", "ssim_q30", "windows")}
+        for c, name in enumerate("yuv"):
+            out["psnr_" + name] = self.lib.hl_amd_psnr_db(out["sse"][c], out["samples"][c])
+            out["ssim_" + name] = self.lib.hl_amd_ssim_mean(out["ssim_q30"][c], out["windows"][c])
+        return out
+
+    def debug_quality_mb(self, k: int, layer: int = 0):
+        """sum (source - reconstruction)^2 of every luma macroblock of that
+        picture, a uint32 array of shape (mbh, mbw) (hl_amd_debug_quality_mb)."""
+        import numpy as np
+
+        mbh, mbw = (self.height << layer) // 16, (self.width << layer) // 16
+        out = np.zeros((mbh, mbw), np.uint32)
+        rc = self.lib.hl_amd_debug_quality_mb(self._h, layer, k, out.ctypes.data, mbh * mbw)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_debug_quality_mb")
+        return out
+
+    def bench_quality(self, iters: int = 50) -> float:
+        """average ms of the last measurement launch of the AVC path, whose
+        planes must still be there; drops the last call's results (diagnostics)"""
+        ms = ctypes.c_float()
+        rc = self.lib.hl_amd_bench_quality(self._h, iters, ctypes.byref(ms))
+        if rc:
+            raise HlAmdError(rc, "hl_amd_bench_quality")
         return ms.value
 
     def bench_planes(self, iters: int = 50) -> float:

@@ -37,6 +37,7 @@
 #include "hl_cavlc.h"
 #include "hl_pyramid.h"
 #include "hl_scene.h"
+#include "hl_quality.h"
 #include "hl_writer.h"
 #endif
 
@@ -1079,11 +1080,29 @@ struct hl_amd_encoder_s {
     std::vector<uint64_t> sc_P, sc_I;            // per frame of the last call (hl_amd_last_scene_stats)
     std::vector<char> sc_analysed, sc_turned;
     std::vector<hl_amd_frame_ctl_t> sc_ctl;      // the last call's effective ctl
+    // per-picture quality (hl_amd_set_quality, hl_quality.h): every coded
+    // picture is compared with the planes it was coded from, one k_quality
+    // launch per group of pictures (an enhancement layer: per picture) on the
+    // stream that produced them; the sums are read back with the group
+    bool q_on = false;
+    bool q_ok = false;                           // the last encode call ended well: its layer-0 results stand
+    bool q_nested = false;                       // inside hl_amd_encode_layers_batch: its base runs fill slots q_off + k
+    int q_off = 0;
+    int q_cap = 0, q_layers = 0;                 // slots per layer and layers the arrays hold
+    unsigned long long* d_q_sums = nullptr;      // [layer][q_cap][plane][2] sse, ssim_q30
+    unsigned long long* h_q_sums = nullptr;      // ... read back (pinned)
+    uint32_t* d_q_mb[4] = {};                    // per layer: [q_cap][MB] luma SSE
+    const uint8_t** d_q_tab = nullptr;           // [kMaxRun][6] source and reconstruction planes of a group's launch
+    const uint8_t** h_q_tab = nullptr;           // ... staged (pinned)
+    std::vector<char> q_valid[4];                // per layer and picture of the last call: measured
+    int q_last_m = 0, q_last_slot = 0;           // the last AVC launch (hl_amd_bench_quality)
 };
 
 static void svc_free(hl_amd_encoder_t* e);
 static hipError_t svc_drain_el(hl_amd_encoder_t* e);
 static bool svc_started(const hl_amd_encoder_t* e);
+static int svc_layer_count(const hl_amd_encoder_t* e);                      // 1 without layers
+static void svc_layer_size(const hl_amd_encoder_t* e, int l, int& W, int& H);
 
 static void free_all(hl_amd_encoder_t* e)
 {
@@ -1107,6 +1126,11 @@ static void free_all(hl_amd_encoder_t* e)
     (void)hipFree(e->d_sc_mb);
     (void)hipFree(e->d_sc_sums);
     (void)hipHostFree(e->h_sc_sums);
+    (void)hipFree(e->d_q_sums);
+    (void)hipHostFree(e->h_q_sums);
+    for (int l = 0; l < 4; ++l) (void)hipFree(e->d_q_mb[l]);
+    (void)hipFree(e->d_q_tab);
+    (void)hipHostFree(e->h_q_tab);
     (void)hipFree(e->d_bpic);
     (void)hipFree(e->d_bpl);
     (void)hipFree(e->d_brec);
@@ -1411,6 +1435,108 @@ static int32_t encode_frame(hl_amd_encoder_t* e, const uint8_t* y, const uint8_t
     --e->gop_left;
     e->since_idr = next_since_idr(e->since_idr, intra);
     ++e->frame_index;
+    return HL_AMD_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------
+// Per-picture quality (hl_amd_set_quality; no reference interface).
+// k_quality (hl_quality.h) compares coded pictures with the planes they were
+// coded from: on the AVC path one launch per group of pictures and encoder,
+// queued by encode_group behind the group's pictures -- before the next group
+// reuses d_bpic -- and read back with the group's closing synchronise; for an
+// enhancement layer one launch per picture on the layers' stream
+// (svc_encode_el), read back with the layer's slice bits.  Results live in
+// slots [layer][picture of the call].
+// ---------------------------------------------------------------------------
+static void quality_drop(hl_amd_encoder_t* e)
+{
+    e->q_ok = false;
+    e->q_last_m = 0;
+    for (int l = 0; l < 4; ++l) e->q_valid[l].clear();
+}
+
+static bool quality_aligned(const hl_amd_encoder_t* e, const uint8_t* y, const uint8_t* u, const uint8_t* v)
+{
+    return !e->q_on || (((uintptr_t)y | (uintptr_t)u | (uintptr_t)v) & 7) == 0;  // k_quality loads 8-byte words
+}
+
+// the start of an encode call of n pictures (access units): the last call's
+// results go, the arrays hold n slots of every layer
+static int32_t quality_begin(hl_amd_encoder_t* e, int n)
+{
+    quality_drop(e);
+    if (!e->q_on) return HL_AMD_SUCCESS;
+    const int layers = svc_layer_count(e);
+    if (n > e->q_cap || layers != e->q_layers) {
+        const int cap = std::max(n, e->q_cap);
+        (void)hipFree(e->d_q_sums);
+        (void)hipHostFree(e->h_q_sums);
+        (void)hipFree(e->d_q_tab);
+        (void)hipHostFree(e->h_q_tab);
+        e->d_q_sums = e->h_q_sums = nullptr;
+        e->d_q_tab = e->h_q_tab = nullptr;
+        for (int l = 0; l < 4; ++l) {
+            (void)hipFree(e->d_q_mb[l]);
+            e->d_q_mb[l] = nullptr;
+        }
+        e->q_cap = e->q_layers = 0;
+        const size_t sums = sizeof(unsigned long long) * 6 * cap * layers, tab = sizeof(uint8_t*) * 6 * kMaxRun;
+        HL_HIP_CHECK(hipMalloc(&e->d_q_sums, sums));
+        HL_HIP_CHECK(hipHostMalloc(&e->h_q_sums, sums, hipHostMallocDefault));
+        HL_HIP_CHECK(hipMalloc(&e->d_q_tab, tab));
+        HL_HIP_CHECK(hipHostMalloc(&e->h_q_tab, tab, hipHostMallocDefault));
+        for (int l = 0; l < layers; ++l) {
+            int W, H;
+            svc_layer_size(e, l, W, H);
+            HL_HIP_CHECK(hipMalloc(&e->d_q_mb[l], sizeof(uint32_t) * (size_t)(W >> 4) * (H >> 4) * cap));
+        }
+        e->q_cap = cap;
+        e->q_layers = layers;
+    }
+    for (int l = 0; l < layers; ++l) e->q_valid[l].assign(n, 0);
+    return HL_AMD_SUCCESS;
+}
+
+// k_quality on m pictures whose table is in d_q_tab, into layer 0's slots from `slot`
+static hipError_t quality_launch_tab(hl_amd_encoder_t* e, int m, int slot)
+{
+    hl::QualityArgs A{};
+    A.tab = e->d_q_tab;
+    A.sums = e->d_q_sums + (size_t)6 * slot;
+    A.mb = e->d_q_mb[0] + (size_t)e->nmb * slot;
+    A.W = e->W;
+    A.H = e->H;
+    return hl::launch_quality(A, m, e->stream);
+}
+
+// The m pictures of a group (their sources Y, U, V; their reconstructions in
+// d_bpic) measured on the encoder's stream into layer 0's slots from base on.
+// The caller synchronises the stream before the next group (h_q_tab, d_bpic).
+static int32_t quality_group(hl_amd_encoder_t* e, int m, const uint8_t* const* Y, const uint8_t* const* U, const uint8_t* const* V, int base)
+{
+    if (!e->q_on) return HL_AMD_SUCCESS;
+    const int slot = e->q_off + base;
+    if (m > kMaxRun || slot + m > e->q_cap || slot + m > (int)e->q_valid[0].size()) return HL_AMD_ERROR_INVALID_STATE;
+    const size_t ys = (size_t)e->W * e->H, cs = ys / 4, pic = ys + 2 * cs;
+    for (int k = 0; k < m; ++k) {
+        const uint8_t** t = e->h_q_tab + 6 * k;
+        const uint8_t* rec = e->d_bpic + pic * k;
+        t[0] = Y[k];
+        t[1] = U[k];
+        t[2] = V[k];
+        t[3] = rec;
+        t[4] = rec + ys;
+        t[5] = rec + ys + cs;
+    }
+    unsigned long long* d = e->d_q_sums + (size_t)6 * slot;
+    const size_t bytes = sizeof(unsigned long long) * 6 * m;
+    HL_HIP_CHECK(hipMemcpyAsync(e->d_q_tab, e->h_q_tab, sizeof(uint8_t*) * 6 * m, hipMemcpyHostToDevice, e->stream));
+    HL_HIP_CHECK(hipMemsetAsync(d, 0, bytes, e->stream));
+    HL_HIP_CHECK(quality_launch_tab(e, m, slot));
+    HL_HIP_CHECK(hipMemcpyAsync(e->h_q_sums + (size_t)6 * slot, d, bytes, hipMemcpyDeviceToHost, e->stream));
+    for (int k = 0; k < m; ++k) e->q_valid[0][slot + k] = 1;
+    e->q_last_m = m;
+    e->q_last_slot = slot;
     return HL_AMD_SUCCESS;
 }
 
@@ -1948,6 +2074,11 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
                 e->last_chain[base + k] = e->h_bchain + nmb * k;
                 e->last_pic[base + k] = dst;
             }
+            if (e->q_on) {  // the pictures as copied into the run buffers, before the next group rewrites them
+                const int32_t rc = quality_group(e, m, Y[si], U[si], V[si], base);
+                if (rc) return rc;
+                HL_HIP_CHECK(hipStreamSynchronize(e->stream));
+            }
             e->reruns = 1;
             continue;
         }
@@ -1982,6 +2113,10 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
             ++e->frame_index;
         }
         e->chain_end = carry;
+        if (e->q_on) {  // (read back by the synchronise below)
+            const int32_t rc = quality_group(e, m, Y[si], U[si], V[si], base);
+            if (rc) return rc;
+        }
         // the last picture of the run becomes the reference
         uint8_t** dst = e->d_pic[e->cur];
         const uint8_t* last = e->d_bpic + pic * (m - 1);
@@ -2154,9 +2289,16 @@ static void scene_commit(hl_amd_encoder_t* e)
 static int32_t encode_pictures(hl_amd_encoder_t* e, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
                                hl_amd_result_t* results, const hl_amd_frame_ctl_t* ctl = nullptr)
 {
+    if (!e->q_nested) quality_drop(e);  // a refused or failed call leaves no results
     if (e->broken) return HL_AMD_ERROR_INVALID_STATE;
+    for (int i = 0; i < n; ++i)
+        if (!quality_aligned(e, y[i], u[i], v[i])) return HL_AMD_ERROR_INVALID_PARAMETER;
     {  // scene cuts of the whole call, before its first run (one launch, however the call is split below)
         const int32_t rc = scene_plan(e, n, y, ctl, &ctl);
+        if (rc) return rc;
+    }
+    if (!e->q_nested) {
+        const int32_t rc = quality_begin(e, n);
         if (rc) return rc;
     }
     begin_call(e, n);
@@ -2167,6 +2309,7 @@ static int32_t encode_pictures(hl_amd_encoder_t* e, int n, const uint8_t* const*
         i += m;
     }
     scene_commit(e);
+    if (!e->q_nested) e->q_ok = true;
     return HL_AMD_SUCCESS;
 }
 
@@ -2191,15 +2334,23 @@ extern "C" int32_t hl_amd_encode_streams_ex(hl_amd_encoder_t* const* encoders, i
         if (e->W != encoders[0]->W || e->H != encoders[0]->H || e->p.device != encoders[0]->p.device) return HL_AMD_ERROR_INVALID_FORMAT;
         if (e->rc || e->svc || e->broken) return HL_AMD_ERROR_INVALID_STATE;
     }
+    for (int s = 0; s < count; ++s) quality_drop(encoders[s]);  // a refused or failed call leaves no results
     for (int s = 0; s < count && ctl; ++s) {
         const int32_t rc = check_ctl(encoders[s], ctl + (size_t)s * n, n);
         if (rc) return rc;
     }
+    for (int s = 0; s < count; ++s)  // quality: every encoder its own setting, its own launches on its own stream
+        for (int i = 0; i < n; ++i)
+            if (!quality_aligned(encoders[s], y[(size_t)s * n + i], u[(size_t)s * n + i], v[(size_t)s * n + i])) return HL_AMD_ERROR_INVALID_PARAMETER;
     // scene cuts: every encoder has its own setting and state, and its own
     // launch on its own stream (a stream with the feature off launches nothing)
     std::vector<const hl_amd_frame_ctl_t*> E(count, nullptr);
     for (int s = 0; s < count; ++s) {
         const int32_t rc = scene_plan(encoders[s], n, y + (size_t)s * n, ctl ? ctl + (size_t)s * n : nullptr, &E[s]);
+        if (rc) return rc;
+    }
+    for (int s = 0; s < count; ++s) {
+        const int32_t rc = quality_begin(encoders[s], n);
         if (rc) return rc;
     }
     for (int s = 0; s < count; ++s) begin_call(encoders[s], n);
@@ -2220,6 +2371,7 @@ extern "C" int32_t hl_amd_encode_streams_ex(hl_amd_encoder_t* const* encoders, i
         i += m;
     }
     for (int s = 0; s < count; ++s) scene_commit(encoders[s]);
+    for (int s = 0; s < count; ++s) encoders[s]->q_ok = true;
     return HL_AMD_SUCCESS;
 }
 
@@ -2270,6 +2422,7 @@ extern "C" int32_t hl_amd_encode_batch_ex(hl_amd_encoder_t* e, int32_t n, const 
     if (!e || n <= 0 || !y || !u || !v || !results) return HL_AMD_ERROR_INVALID_PARAMETER;
     for (int i = 0; i < n; ++i)
         if (!y[i] || !u[i] || !v[i]) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->q_nested) quality_drop(e);
     if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;  // frames still queued by the look-ahead come first (hl_amd_flush)
     const int32_t rc = check_ctl(e, ctl, n);
     if (rc) return rc;
@@ -2355,6 +2508,7 @@ extern "C" int32_t hl_amd_encode_device_ex(hl_amd_encoder_t* e, const uint8_t* y
                                            const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* r)
 {
     if (!e || !y || !u || !v || !r) return HL_AMD_ERROR_INVALID_PARAMETER;
+    quality_drop(e);
     if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;  // frames still queued by the look-ahead come first (hl_amd_flush)
     const int32_t rc = check_ctl(e, ctl, 1);
     if (rc) return rc;
@@ -2500,6 +2654,93 @@ extern "C" int32_t hl_amd_bench_scene(hl_amd_encoder_t* e, int32_t iters, float*
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
     return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_set_quality(hl_amd_encoder_t* e, int32_t enable)
+{
+    if (!e) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;  // queued frames come first (hl_amd_flush)
+    if ((enable != 0) != e->q_on) quality_drop(e);
+    e->q_on = enable != 0;  // (the arrays come with the first measured call: quality_begin)
+    return HL_AMD_SUCCESS;
+}
+
+// is picture k of layer `layer` of the last call measured, and its sums on the host?
+static bool quality_have(const hl_amd_encoder_t* e, int32_t layer, int32_t k)
+{
+    if (!e->q_on || layer >= e->q_layers || k >= (int)e->q_valid[layer].size() || !e->q_valid[layer][k]) return false;
+    return layer > 0 || e->q_ok;
+}
+
+extern "C" int32_t hl_amd_last_quality(hl_amd_encoder_t* e, int32_t layer, int32_t k, hl_amd_quality_t* out)
+{
+    if (!e || !out || layer < 0 || layer > 3 || k < 0) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!quality_have(e, layer, k)) return HL_AMD_ERROR_INVALID_STATE;
+    int W, H;
+    svc_layer_size(e, layer, W, H);
+    const unsigned long long* s = e->h_q_sums + (size_t)6 * ((size_t)layer * e->q_cap + k);
+    for (int c = 0; c < 3; ++c) {
+        const uint64_t w = c ? W >> 1 : W, h = c ? H >> 1 : H;
+        out->sse[c] = s[2 * c];
+        out->samples[c] = w * h;
+        out->ssim_q30[c] = (int64_t)s[2 * c + 1];
+        out->windows[c] = (w / 4 - 1) * (h / 4 - 1);
+    }
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_debug_quality_mb(hl_amd_encoder_t* e, int32_t layer, int32_t k, uint32_t* sse_y, size_t mbs)
+{
+    if (!e || !sse_y || layer < 0 || layer > 3 || k < 0) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!quality_have(e, layer, k)) return HL_AMD_ERROR_INVALID_STATE;
+    int W, H;
+    svc_layer_size(e, layer, W, H);
+    const size_t nmb = (size_t)(W >> 4) * (H >> 4);
+    if (mbs != nmb) return HL_AMD_ERROR_INVALID_PARAMETER;
+    HL_HIP_CHECK(hipMemcpyAsync(sse_y, e->d_q_mb[layer] + nmb * k, sizeof(uint32_t) * nmb, hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipStreamSynchronize(e->stream));
+    return HL_AMD_SUCCESS;
+}
+
+// k_quality alone: `iters` times the last measurement launch of the AVC path
+// (the table it left in d_q_tab; the planes must still be there), timed with
+// HIP events on the encoder's stream; *ms = average milliseconds per launch.
+// The sums it adds into are dropped.  Diagnostics, like hl_amd_bench_scene.
+extern "C" int32_t hl_amd_bench_quality(hl_amd_encoder_t* e, int32_t iters, float* ms)
+{
+    if (!e || iters <= 0 || !ms) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->q_on || !e->q_ok || !e->q_last_m) return HL_AMD_ERROR_INVALID_STATE;  // no launch to repeat
+    const int m = e->q_last_m, slot = e->q_last_slot;
+    quality_drop(e);
+    hipEvent_t a, b;
+    HL_HIP_CHECK(hipEventCreate(&a));
+    HL_HIP_CHECK(hipEventCreate(&b));
+    HL_HIP_CHECK(quality_launch_tab(e, m, slot));  // warm
+    HL_HIP_CHECK(hipEventRecord(a, e->stream));
+    for (int i = 0; i < iters; ++i) HL_HIP_CHECK(quality_launch_tab(e, m, slot));
+    HL_HIP_CHECK(hipEventRecord(b, e->stream));
+    HL_HIP_CHECK(hipEventSynchronize(b));
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, a, b);
+    *ms = t / iters;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" double hl_amd_psnr_db(uint64_t sse, uint64_t samples)
+{
+    if (!samples) return NAN;
+    if (!sse) return INFINITY;
+    return 10.0 * log10(65025.0 * (double)samples / (double)sse);
+}
+
+extern "C" double hl_amd_ssim_mean(int64_t q30, uint64_t windows)
+{
+    if (!windows || windows > (1ull << 33)) return NAN;
+    const int64_t lim = (int64_t)(windows << 30);
+    if (q30 > lim || q30 < -lim) return NAN;
+    return (double)q30 / 1073741824.0 / (double)windows;
 }
 
 extern "C" int32_t hl_amd_flush(hl_amd_encoder_t* e, hl_amd_result_t* r)
@@ -2737,6 +2978,7 @@ struct SvcLayerDev {
     size_t words_bytes, esd_size;
     std::future<size_t> writing;  // the slice, written by a host thread while the GPU codes the next layer
     uint8_t* d_snap;              // the reference picture at the start of a layers batch (its redo after a base re-encode)
+    int q_slot = -1;              // quality: the slot the picture under way is measured into (valid once its slice is joined)
 };
 
 struct SvcState {
@@ -2752,6 +2994,7 @@ struct SvcState {
     int32_t* d_unpinned = nullptr;
     int32_t unpinned = 0;
     float ms_el = 0.f;               // enhancement-layer device time of the last access unit
+    int q_k = 0;                     // quality: the access unit of the call (the slot of its enhancement-layer pictures)
     // hl_amd_encode_layers_batch: the base layer of access unit i as the
     // reference layer (picture of the base run, MB objects from its records)
     uint8_t* ref0_pic[3] = {nullptr, nullptr, nullptr};
@@ -2784,6 +3027,12 @@ struct SvcState {
 };
 
 static bool svc_started(const hl_amd_encoder_t* e) { return e->svc && e->svc->started; }
+static int svc_layer_count(const hl_amd_encoder_t* e) { return e->svc && !e->svc->w.empty() ? (int)e->svc->w.size() : 1; }
+static void svc_layer_size(const hl_amd_encoder_t* e, int l, int& W, int& H)
+{
+    W = l ? e->svc->w[l] : e->W;
+    H = l ? e->svc->h[l] : e->H;
+}
 
 static void svc_free(hl_amd_encoder_t* e)
 {
@@ -2979,6 +3228,25 @@ static int32_t svc_encode_el(hl_amd_encoder_t* e, int l, const uint8_t* y, const
         k_deblock_rows<<<L.mbh, 64, 0, st>>>(D, L.d_rows, L.d_rows + L.mbh);
         HL_HIP_CHECK(hipGetLastError());
     }
+    // quality: the finished picture against the layer's input, on the layer's
+    // stream; its sums reach the host with the slice bits (ev_rec below)
+    L.q_slot = -1;
+    if (e->q_on && l < e->q_layers && s->q_k < (int)e->q_valid[l].size()) {
+        const size_t slot = (size_t)l * e->q_cap + s->q_k;
+        hl::QualityArgs Q{};
+        Q.one[0] = y;
+        Q.one[1] = u;
+        Q.one[2] = v;
+        for (int c = 0; c < 3; ++c) Q.one[3 + c] = cur[c];
+        Q.sums = e->d_q_sums + 6 * slot;
+        Q.mb = e->d_q_mb[l] + (size_t)L.nmb * s->q_k;
+        Q.W = L.W;
+        Q.H = L.H;
+        HL_HIP_CHECK(hipMemsetAsync(Q.sums, 0, sizeof(unsigned long long) * 6, st));
+        HL_HIP_CHECK(hl::launch_quality(Q, 1, st));
+        HL_HIP_CHECK(hipMemcpyAsync(e->h_q_sums + 6 * slot, Q.sums, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, st));
+        L.q_slot = s->q_k;
+    }
     // slice data serialised on the GPU (hl_cavlc.h)
     {
         const int nb = (L.nmb + 63) / 64;
@@ -3032,6 +3300,8 @@ static int32_t svc_join(hl_amd_encoder_t* e, int upto)
             rc = HL_AMD_ERROR_TOOSHORT;
             continue;
         }
+        if (L.q_slot >= 0 && L.q_slot < (int)e->q_valid[l].size()) e->q_valid[l][L.q_slot] = 1;  // (its sums came with the slice bits)
+        L.q_slot = -1;
         if (!s->au.empty()) s->au.insert(s->au.end(), scp, scp + 3);
         s->au.insert(s->au.end(), L.out.data() + 3, L.out.data() + n);
         if (e->timing) {
@@ -3109,6 +3379,11 @@ extern "C" int32_t hl_amd_encode_layer(hl_amd_encoder_t* e, int32_t width, int32
     int32_t rc = svc_start(e);
     if (rc != HL_AMD_SUCCESS) return rc;
     if (l != s->next || l < s->first || l > s->last) return HL_AMD_ERROR_INVALID_STATE;
+    if (l > 0) {  // quality (layer 0: the AVC path's own checks)
+        if (on_device && !quality_aligned(e, y, u, v)) return HL_AMD_ERROR_INVALID_PARAMETER;
+        if (l == s->first && (rc = quality_begin(e, 1))) return rc;  // an access unit that starts above the base layer
+    }
+    s->q_k = 0;
     r->type = 0;
     r->data = nullptr;
     r->data_size = 0;
@@ -3318,6 +3593,9 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
     // under rate control every base picture takes the per-picture path and no
     // run keeps the pictures' records: code such streams with hl_amd_encode_layer
     if (e->rc) return HL_AMD_ERROR_NOT_IMPLEMENTED;
+    quality_drop(e);  // a refused or failed batch leaves no results
+    for (int i = 0; i < 3 * n * layers; i += 3)
+        if (!quality_aligned(e, planes[i], planes[i + 1], planes[i + 2])) return HL_AMD_ERROR_INVALID_PARAMETER;
     const size_t nmb0 = e->nmb, ys = (size_t)e->W * e->H, cs = ys / 4, pic = ys + 2 * cs;
     const int chunk = std::min(n, kMaxRun);
     if (s->bst_cap < (size_t)chunk) {
@@ -3342,6 +3620,7 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
         --gl;
     }
     if (e->broken) return HL_AMD_ERROR_INVALID_STATE;
+    if ((rc = quality_begin(e, n))) return rc;  // slots of the whole batch: access unit i's pictures go to slot i of their layers
     // what the caller queued on the encoder's stream before comes first
     HL_HIP_CHECK(hipEventRecord(s->ev_fork, e->stream));
     HL_HIP_CHECK(hipStreamWaitEvent(s->est, s->ev_fork, 0));
@@ -3363,6 +3642,10 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
         ~Restore()
         {
             e->pipe_wg = saved_wg;
+            e->q_nested = false;
+            e->q_off = 0;
+            if (ok) e->q_ok = true;
+            else quality_drop(e);
             s->linked = true;
             s->ref0_st = nullptr;
             for (int c = 0; c < 3; ++c) s->ref0_pic[c] = nullptr;
@@ -3371,6 +3654,7 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
             if (!joined || (!ok && el_ahead.load())) e->broken = true;
         }
     } restore{e, s, e->pipe_wg, el_ahead};
+    e->q_nested = true;  // the base runs below measure into this batch's slots, chunk by chunk (q_off)
     std::atomic<bool> base_done{false};
     constexpr int32_t kAborted = -1;  // the run fell back while the thread coded from it
     // the enhancement layers of access units [i0, i0 + m) (base pictures
@@ -3418,6 +3702,7 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
             s->au_intra = intra[i] != 0;
             s->au.clear();
             s->ms_el = 0.f;
+            s->q_k = i;
             std::vector<uint8_t>& hdr = s->elhdr[i];
             hdr.clear();
             el_ahead.store(true);
@@ -3472,6 +3757,7 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
         // again, and sets it only when this run falls back)
         e->run_aborted.store(false, std::memory_order_release);
         std::future<int32_t> el = std::async(std::launch::async, el_chunk, i0, m, true);
+        e->q_off = i0;
         rc = hl_amd_encode_batch(e, m, Y.data(), U.data(), V.data(), br.data());
         base_done.store(true, std::memory_order_release);
         int32_t rel = el.get();

@@ -507,6 +507,63 @@ int32_t hl_amd_debug_scene_mb(hl_amd_encoder_t* encoder, int32_t k, uint32_t* in
  * reference interface (like hl_amd_bench_pyramid). */
 int32_t hl_amd_bench_scene(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
 
+/* Per-picture quality: PSNR and SSIM sums of every coded picture against the
+ * planes it was coded from, computed on the GPU while both are resident
+ * (k_quality, hl_quality.h).  No reference interface: the reference has
+ * nothing that measures a coded picture.  It changes no byte of any stream.
+ * Integers only, exact in any order.  Per plane c (0 Y, 1 U, 2 V), with a =
+ * source and b = deblocked reconstruction:
+ *   sse[c]      = sum (a - b)^2                  samples[c] = the plane's W H
+ *   ssim_q30[c] = sum over the plane's 8x8 windows (stride 4: (W/4 - 1)
+ *                 (H/4 - 1) = windows[c] of them) of floor(num 2^30 / den),
+ *     S1 = sum a, S2 = sum b, SS = sum (a^2 + b^2), S12 = sum a b of the window,
+ *     num = (2 S1 S2 + 416)(2 (64 S12 - S1 S2) + 235963),
+ *     den = (S1^2 + S2^2 + 416)(64 SS - S1^2 - S2^2 + 235963).
+ * hl_amd_psnr_db and hl_amd_ssim_mean turn them into the usual figures. */
+typedef struct hl_amd_quality_s {
+    uint64_t sse[3], samples[3];
+    int64_t ssim_q30[3];
+    uint64_t windows[3];
+} hl_amd_quality_t;
+
+/* enable 0: off (the default; nothing is launched or allocated), else on.
+ * Honoured by hl_amd_encode, _device, _batch, _streams (every encoder its own
+ * setting), their _ex forms, the look-ahead queue (measured when the queue is
+ * coded), rate-controlled encoders and, on encoders with layers, every layer
+ * this encoder codes (hl_amd_encode_layer, _au: k = 0; hl_amd_encode_layers_batch,
+ * hl_amd_encode_aus_batch: k = the access unit).  While the feature is on,
+ * device planes must be 8-byte aligned: a call with another plane returns
+ * HL_AMD_ERROR_INVALID_PARAMETER before anything is coded.  Between any two
+ * encode calls; while look-ahead frames are queued
+ * HL_AMD_ERROR_INVALID_STATE.  No reference interface (see above). */
+int32_t hl_amd_set_quality(hl_amd_encoder_t* encoder, int32_t enable);
+
+/* Picture k of layer `layer` (0 on encoders without layers) of the last
+ * encode call (with look-ahead: the call that coded the queue).
+ * HL_AMD_ERROR_INVALID_STATE when that picture or layer was not measured: the
+ * feature was off, the layer is coded elsewhere (hl_amd_set_layer_range), or
+ * the last call was refused or failed.  No reference interface (see above). */
+int32_t hl_amd_last_quality(hl_amd_encoder_t* encoder, int32_t layer, int32_t k, hl_amd_quality_t* out);
+
+/* Diagnostics: sum (a - b)^2 of every 16x16 luma macroblock (mbs = the
+ * layer's macroblock count) of that picture; the same refusals.  No
+ * reference interface (the tests' handle on k_quality). */
+int32_t hl_amd_debug_quality_mb(hl_amd_encoder_t* encoder, int32_t layer, int32_t k, uint32_t* sse_y, size_t mbs);
+
+/* Diagnostics: `iters` times the last measurement launch of the AVC path (the
+ * same planes, which must still be there, into the same sums, which are
+ * unusable afterwards: hl_amd_last_quality returns HL_AMD_ERROR_INVALID_STATE
+ * until the next encode call); *ms = average ms per launch.
+ * HL_AMD_ERROR_INVALID_STATE without such a launch.  No reference interface
+ * (like hl_amd_bench_scene). */
+int32_t hl_amd_bench_quality(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
+
+/* Pure functions (no device): 10 log10(255^2 samples / sse), +infinity for
+ * sse = 0, NaN for samples = 0; and q30 / 2^30 / windows, NaN for windows = 0
+ * or |q30| > windows 2^30.  No reference interface (see above). */
+double hl_amd_psnr_db(uint64_t sse, uint64_t samples);
+double hl_amd_ssim_mean(int64_t q30, uint64_t windows);
+
 /* device time (ms) of the enhancement layers of the last access unit (with
  * hl_amd_set_timing on) */
 float hl_amd_svc_layer_ms(hl_amd_encoder_t* encoder);

@@ -19,6 +19,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "hartallo_amd.h" /* include/hartallo_amd.h of the gfx950 library */
 
@@ -36,6 +37,13 @@ typedef struct hl_codec_264_gfx950_s {
     int input_type;          /* GFX950_* */
     int32_t open_me_range, open_deblock, open_early_term, open_gop_size; /* the settings the encoder was opened with */
     hl_codec_t* dec;         /* stock H.264 codec that decodes for this object (created on the first decode) */
+    /* HL_AMD_QUALITY=1 (gfx950_open): pictures reported so far, frames the look-ahead queues (its depth: lookahead),
+     * and the last reported picture's sums per layer (hl_codec_264_gfx950_last_quality) */
+    int quality, lookahead;
+    long q_pictures;
+    int q_queued;
+    hl_amd_quality_t q_last[4];
+    int q_have[4];
 } hl_codec_264_gfx950_t;
 
 static hl_object_t* gfx950_ctor(hl_object_t* self, va_list* app)
@@ -93,6 +101,22 @@ static HL_ERROR_T gfx950_open(hl_codec_264_gfx950_t* self, hl_codec_t* base, hl_
         const char* la = getenv("HL_AMD_LOOKAHEAD");
         if (la && atoi(la) > 1 && (err = hl_amd_set_lookahead(self->enc, atoi(la)))) return (HL_ERROR_T)err;
     }
+    self->lookahead = 1;
+    {
+        const char* la = getenv("HL_AMD_LOOKAHEAD");
+        if (la && atoi(la) > 1) self->lookahead = atoi(la);
+    }
+    /* per-picture quality (opt-in, no reference counterpart): HL_AMD_QUALITY=1
+     * switches hl_amd_set_quality on; every coded picture and layer is then
+     * reported on stderr (gfx950_report_quality) */
+    {
+        const char* q = getenv("HL_AMD_QUALITY");
+        self->quality = q && atoi(q) > 0;
+        self->q_pictures = 0;
+        self->q_queued = 0;
+        memset(self->q_have, 0, sizeof(self->q_have));
+        if (self->quality && (err = hl_amd_set_quality(self->enc, 1))) return (HL_ERROR_T)err;
+    }
     /* scene-cut detection (opt-in, no reference counterpart):
      * HL_AMD_SCENECUT=threshold[:min_gap[:range]] (hl_amd_set_scenecut; 0 =
      * off).  A frame the detector finds to be a cut is coded as if its
@@ -138,6 +162,36 @@ static HL_ERROR_T gfx950_open(hl_codec_264_gfx950_t* self, hl_codec_t* base, hl_
     self->open_deblock = p.deblock;
     self->open_early_term = p.me_early_term;
     self->open_gop_size = p.gop_size;
+    return HL_ERROR_SUCCESS;
+}
+
+/* HL_AMD_QUALITY: pictures [0, n) of the encoder's last call, layers [0, layers), one line each:
+ *   hl_codec_264_gfx950: quality picture N layer L psnr Y U V ssim Y U V
+ * (N counts coded pictures / access units from 0; PSNR in dB with 6 decimals, "inf" for an identical plane; SSIM with 8) */
+static void gfx950_report_quality(hl_codec_264_gfx950_t* self, int n, int layers)
+{
+    int k, l;
+    for (k = 0; k < n; ++k, ++self->q_pictures)
+        for (l = 0; l < layers && l < 4; ++l) {
+            hl_amd_quality_t q;
+            self->q_have[l] = hl_amd_last_quality(self->enc, l, k, &q) == HL_AMD_SUCCESS;
+            if (!self->q_have[l]) continue;
+            self->q_last[l] = q;
+            fprintf(stderr, "hl_codec_264_gfx950: quality picture %ld layer %d psnr %.6f %.6f %.6f ssim %.8f %.8f %.8f\n", self->q_pictures, l,
+                    hl_amd_psnr_db(q.sse[0], q.samples[0]), hl_amd_psnr_db(q.sse[1], q.samples[1]), hl_amd_psnr_db(q.sse[2], q.samples[2]),
+                    hl_amd_ssim_mean(q.ssim_q30[0], q.windows[0]), hl_amd_ssim_mean(q.ssim_q30[1], q.windows[1]),
+                    hl_amd_ssim_mean(q.ssim_q30[2], q.windows[2]));
+        }
+}
+
+/* The sums of the last reported picture's layer (HL_AMD_QUALITY=1), next to
+ * hl_codec_264_gfx950_flush: HL_ERROR_INVALID_STATE when nothing was measured. */
+HL_ERROR_T hl_codec_264_gfx950_last_quality(hl_codec_t* base, int32_t layer, hl_amd_quality_t* out)
+{
+    hl_codec_264_gfx950_t* self = (hl_codec_264_gfx950_t*)base;
+    if (!self || !out || layer < 0 || layer > 3) return HL_ERROR_INVALID_PARAMETER;
+    if (!self->enc || !self->quality || !self->q_have[layer]) return HL_ERROR_INVALID_STATE;
+    *out = self->q_last[layer];
     return HL_ERROR_SUCCESS;
 }
 
@@ -221,6 +275,7 @@ static HL_ERROR_T gfx950_encode(hl_codec_t* base, const hl_frame_t* frame, hl_co
         if ((err = hl_amd_encode_layer(self->enc, (int32_t)f->data_width[0], (int32_t)f->data_height[0], f->data_ptr[0],
                                        f->data_ptr[1], f->data_ptr[2], 0, &r)))
             return (HL_ERROR_T)err;
+        if (self->quality && (r.type & HL_AMD_RESULT_TYPE_DATA)) gfx950_report_quality(self, 1, (int)L); /* the access unit's last layer */
     }
     else {
         if (!self->enc || self->layers || f->data_width[0] != self->width || f->data_height[0] != self->height)
@@ -237,6 +292,10 @@ static HL_ERROR_T gfx950_encode(hl_codec_t* base, const hl_frame_t* frame, hl_co
         ctl.gop_size = base->gop_size;
         if ((err = hl_amd_encode_ex(self->enc, f->data_ptr[0], f->data_ptr[1], f->data_ptr[2], &ctl, &r)))
             return (HL_ERROR_T)err;
+        if (self->quality && ++self->q_queued == self->lookahead) { /* this call coded the queue (without look-ahead: the frame) */
+            gfx950_report_quality(self, self->q_queued, 1);
+            self->q_queued = 0;
+        }
     }
     gfx950_result(base, &r, result);
     result->width = f->data_width[0];
@@ -257,6 +316,10 @@ HL_ERROR_T hl_codec_264_gfx950_flush(hl_codec_t* base, hl_codec_result_t* result
     result->type = HL_CODEC_RESULT_TYPE_NONE;
     if (!self->enc || self->layers) return HL_ERROR_SUCCESS;
     if ((err = hl_amd_flush(self->enc, &r))) return (HL_ERROR_T)err;
+    if (self->quality && self->q_queued) { /* this call coded what was still queued */
+        gfx950_report_quality(self, self->q_queued, 1);
+        self->q_queued = 0;
+    }
     gfx950_result(base, &r, result);
     result->width = self->width;
     result->height = self->height;
