@@ -4,6 +4,7 @@
 #   tests/emu/libhl_pyr_emu.so       test-only host build of the layer pyramid (hl_pyramid.h)
 #   tests/emu/libhl_scene_emu.so     test-only host build of the scene-cut analysis (hl_scene.h)
 #   tests/emu/libhl_quality_emu.so   test-only host build of the quality metric (hl_quality.h)
+#   tests/emu/libhl_sched_emu.so     test-only host build of the pipelined run's pop (hl_sched.h)
 #   tests/emu/libhl_rec_emu.so       test-only host exports of the candidate record's pack / unpack (hl_mbcore.h)
 #   tests/gpu_unit/libhl_unit.so     test-only GPU unit kernels (coop pipeline vs scalar primitives)
 #   tests/gpu_unit/libhl_unit_cand.so  test-only GPU unit kernel (the search's candidate slot)
@@ -29,7 +30,7 @@ DEVFLAGS := -mllvm -amdgpu-sched-strategy=iterative-ilp
 all: product emu unit oracle sanitize
 
 product: hartallo_amd/libhartallo_amd.so
-emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_rec_emu.so
+emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so
 unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so
 
 hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
@@ -55,6 +56,10 @@ tests/emu/libhl_scene_emu.so: tests/emu/hl_scene_emu.cpp $(CSRC)/hl_scene.h
 tests/emu/libhl_quality_emu.so: tests/emu/hl_quality_emu.cpp $(CSRC)/hl_quality.h
 	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_quality_emu.cpp
 
+# the pop's key, choice, head rule and slot / claim transitions on the host (no device code)
+tests/emu/libhl_sched_emu.so: tests/emu/hl_sched_emu.cpp $(CSRC)/hl_sched.h
+	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_sched_emu.cpp
+
 # the candidate record's pack and unpack functions on the host (no device code)
 tests/emu/libhl_rec_emu.so: tests/emu/hl_rec_emu.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -O2 --cuda-host-only -shared -o $@ tests/emu/hl_rec_emu.hip
@@ -75,11 +80,13 @@ tests/gpu_unit/libhl_unit_rec.so: tests/gpu_unit/hl_unit_rec.hip $(HDRS)
 #       UndefinedBehaviorSanitizer; run with the clang ASan runtime preloaded
 #   tests/sanitize/rowgate_tsan  the pipelined run's row-gated slice writers
 #       (hl_writer.h RowGate) under ThreadSanitizer
+#   tests/sanitize/pop_tsan  the pipelined run's pop protocol (hl_sched.h with
+#       task_deps / task_succ) on 16 threads under ThreadSanitizer
 # (hipcc: every -fsanitize= directly after -Xarch_host, host code only)
 SANFLAGS := -std=c++17 -O1 -g -fno-omit-frame-pointer -fPIC -ffp-contract=off -Wno-unused-function -Wno-unused-variable
 ASAN := -Xarch_host -fsanitize=address
 UBSAN := -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined
-sanitize: tests/sanitize/libhl_emu_asan.so tests/sanitize/rowgate_tsan
+sanitize: tests/sanitize/libhl_emu_asan.so tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan
 tests/sanitize/hl_writer_asan.o: $(CSRC)/hl_writer.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) $(ASAN) $(UBSAN) -c -o $@ $<
 tests/sanitize/hl_rc_asan.o: $(CSRC)/hl_rc.cpp $(HDRS)
@@ -90,6 +97,8 @@ tests/sanitize/libhl_emu_asan.so: tests/sanitize/hl_emu_asan.o tests/sanitize/hl
 	$(HIPCC) --offload-arch=$(ARCH) $(ASAN) $(UBSAN) -shared-libsan -shared -o $@ $^
 tests/sanitize/rowgate_tsan: tests/sanitize/rowgate_tsan.cpp $(CSRC)/hl_writer.cpp $(HDRS)
 	$(HIPCC) $(SANFLAGS) -Xarch_host -fsanitize=thread -o $@ tests/sanitize/rowgate_tsan.cpp $(CSRC)/hl_writer.cpp -lpthread
+tests/sanitize/pop_tsan: tests/sanitize/pop_tsan.cpp $(HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) -Xarch_host -fsanitize=thread -o $@ -x hip tests/sanitize/pop_tsan.cpp -lpthread
 # the emulator under UndefinedBehaviorSanitizer too: a 16-minute compile of
 # the kernel logic, run once per change of the shift / overflow idioms
 # (DESIGN.md §2); tests/test_sanitizers.py uses it when it is present
@@ -132,5 +141,5 @@ oracle: product  # oracle/_ref/drop_in_enc links the product library
 	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
-	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_rec_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan
+	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan
 	$(MAKE) -C oracle clean

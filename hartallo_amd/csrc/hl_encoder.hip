@@ -301,6 +301,17 @@ constexpr int kSubQ = HL_SUBQ;
 #define HL_SCAN 4
 #endif
 constexpr int kScan = HL_SCAN;
+// Profiling words behind the 64 phase words and the per-MB timeline (4 per
+// MB): the barrier sites of an HL_BAR_PROF=2 build, then the pop's
+// (pop_task: cycles of lost, nothing-ready, winning and stood-back rounds,
+// stood-back rounds, slots seen taken, head advances, and the pop time of
+// rounds that ended in a helper task, which prof[40] does not hold)
+#if defined(HL_PROFILE) && defined(HL_BAR_PROF) && HL_BAR_PROF >= 2
+constexpr int kProfSites = 2 * kBarSites;
+#else
+constexpr int kProfSites = 0;
+#endif
+constexpr int kProfPop = 8;
 
 #if !defined(HL_KERNELS_ONLY)
 // Dependency counters and ready queues of a run (hl_pipeline.h): only task
@@ -325,6 +336,7 @@ __global__ __launch_bounds__(256) void k_pipe_init(PipeArgs P, int mbw, int mbh)
         P.tail[i] = (i / kSubQ) % P.spp == 0 && i % kSubQ == 0 ? 1 : 0;
     }
     if (i < P.nstreams) P.oldest[i] = 0;
+    if (i == 0) *P.poppers = 0;
     if (i < kHelperQ) {
         P.hq_head[i] = 0;
         P.hq_tail[i] = 0;
@@ -339,6 +351,23 @@ __global__ __launch_bounds__(256) void k_pipe_init(PipeArgs P, int mbw, int mbh)
 // the run has finished (or after ~10 s without a task: a wait gave up
 // somewhere and the host re-encodes the run).  A queue entry whose claim
 // fails was taken by workgroup 0 (claim_next) and is skipped.
+//
+// The hand-over (hl_sched.h): a round reads, per lane, the head and tail of
+// kScan sub-queues and then the slots of each head's aligned group (kPopLook);
+// it takes an entry with a CAS on the slot word itself, so two workgroups
+// that see several ready entries take different ones instead of racing for
+// one head word.  Among the lanes whose best entry lies within kPopSpread
+// steps of the wave's best, the round tries the k-th, k from a sequence that
+// starts at blockIdx and moves on after every lost or skipped round, modulo
+// the workgroups inside pop_task (P.poppers), then modulo those lanes.  One
+// popper alone takes the best entry.  With more poppers than entries a popper
+// whose k is not below kPopOversub times the entries makes no attempt in that
+// round (kPopStandBack rounds in a row at most; sched_choose states the bias
+// this gives a pop's first round): hundreds of failed CASes on the
+// few ready slot words are what made a lost round long.  The round waits for
+// nothing: a slot still 0
+// (pushed, not yet written) is skipped, a taken one is skipped and the head
+// moved past it; a round that finds nothing backs off and scans again.
 //
 // Which picture's queue head: with P.hop < 0 the oldest picture's; else the
 // head with the longest remaining dependency path to the end of the run
@@ -358,22 +387,47 @@ __global__ __launch_bounds__(256) void k_pipe_init(PipeArgs P, int mbw, int mbh)
 // finished ones, with empty queues)
 __device__ int pop_task(const PipeArgs& P, int nmb, int mbw, int mbh, int& olc, const SchedRecip& rc
 #if defined(HL_PROFILE)
-                        , unsigned long long* pst  // profiling: [0] attempts on a macroblock, [1] lost, [2] empty rounds
+                        , unsigned long long* pst  // profiling: [0] attempts on a macroblock, [1] lost, [2] rounds with nothing ready,
+                                                   // [3..5] cycles of lost / nothing-ready / winning rounds (a round that ends in a
+                                                   // helper task counts as winning), [6] slots seen taken, [7] head advances,
+                                                   // [8] rounds stood back, [9] their cycles (back-off included, as for [4])
 #endif
 )
 {
+    static_assert(64 % kSubQ == 0 && (kPopLook == 4 || kPopLook == 2), "a lane's sub-queue is lane % kSubQ; a head's group is one or two 8-byte loads");
     const int lane = __lane_id();
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
     int empty = 0;
+    uint32_t seq = blockIdx.x;
+    int stood_back = 0;  // rounds in a row without an attempt (kPopOversub)
+    // workgroups inside pop_task (fetch-adds: they never retry)
+    if (lane == 0) __hip_atomic_fetch_add(P.poppers, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#define HL_POP_RETURN(t)                                                                                  \
+    do {                                                                                                  \
+        if (lane == 0) __hip_atomic_fetch_add(P.poppers, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+        return (t);                                                                                       \
+    } while (0)
+#if defined(HL_PROFILE)
+    unsigned long long pc = __builtin_readcyclecounter();
+#define HL_POPCYC(i)                                                    \
+    do {                                                                \
+        const unsigned long long now_ = __builtin_readcyclecounter();   \
+        pst[i] += now_ - pc;                                            \
+        pc = now_;                                                      \
+    } while (0)
+#else
+#define HL_POPCYC(i) ((void)0)
+#endif
     for (;;) {
         // entry e = lane + 64 i (kScan per lane) = (sub-queue e % kSubQ,
         // stream r % S, its picture oldest + r / S) with r = e / kSubQ: the
         // window of each stream's first unfinished pictures
         const int S = P.nstreams;
-        int oln = 0;
+        int oln = 0, pp = 1;
         if (lane < S) oln = ld_relaxed(P.oldest + lane);
+        if (lane == 63) pp = ld_relaxed(P.poppers);  // (in flight with the heads and tails)
         const int ol = P.nframes > 1 && olc >= 0 ? olc : oln;  // (a lone picture: idle workgroups poll at the read's pace)
-        int fl[kScan], ql[kScan], hs[kScan], ts[kScan], js[kScan], sqs[kScan];
+        int fl[kScan], ql[kScan], hs[kScan], ts[kScan], js[kScan];
         bool ins[kScan];
 #pragma unroll
         for (int i = 0; i < kScan; ++i) {
@@ -383,7 +437,6 @@ __device__ int pop_task(const PipeArgs& P, int nmb, int mbw, int mbh, int& olc, 
             fl[i] = sj * P.spp + k;  // picture slot, its sub-queue
             ql[i] = fl[i] * kSubQ + sq;
             js[i] = j;
-            sqs[i] = sq;
             hs[i] = ts[i] = 0;
             if (ins[i]) {
                 hs[i] = ld_relaxed(P.head + ql[i]);
@@ -391,88 +444,133 @@ __device__ int pop_task(const PipeArgs& P, int nmb, int mbw, int mbh, int& olc, 
             }
         }
         olc = oln;
-        if (__ballot(lane < S && oln < P.spp) == 0) return -1;  // every stream finished
-        int i0 = -1, hh = 0, v = 0, bfl = 0, bql = 0;
-        if (P.hop < 0) {
-            // oldest first: the first non-empty entry
-            unsigned long long bal = 0;
-            int bh = 0;
+        if (__ballot(lane < S && oln < P.spp) == 0) HL_POP_RETURN(-1);  // every stream finished
+        const int poppers = __builtin_amdgcn_readlane(pp, 63);
+        // The slots of each head's aligned group (the words stay
+        // inside the queue allocation: the helper FIFOs follow the last
+        // sub-queue), those outside [head, tail) masked to 0: > 0 ready,
+        // < 0 taken, 0 nothing (or pushed and not yet written: skipped).
+        int32_t qv[kScan][kPopLook];
+        int p0[kScan];  // queue position of qv[i][0] (negative where the group starts in the row before)
 #pragma unroll
-            for (int i = 0; i < kScan && !bal; ++i) {
-                bal = __ballot(ins[i] && hs[i] < ts[i]);
-                if (bal) {
-                    i0 = __ffsll((long long)bal) - 1;
-                    bh = __builtin_amdgcn_readlane(hs[i], i0);
-                    bfl = __builtin_amdgcn_readlane(fl[i], i0);
-                    bql = __builtin_amdgcn_readlane(ql[i], i0);
+        for (int i = 0; i < kScan; ++i) {
+#pragma unroll
+            for (int s = 0; s < kPopLook; ++s) qv[i][s] = 0;
+            p0[i] = 0;
+            if (ins[i] && hs[i] < ts[i]) {
+                const int base = ql[i] * nmb, g = (base + hs[i]) & ~(kPopLook - 1);
+                p0[i] = g - base;
+#pragma unroll
+                for (int s = 0; s < kPopLook; s += 2) {
+                    const uint64_t two = ld_relaxed64((const uint64_t*)(P.queue + g + s));
+                    qv[i][s] = (int32_t)(uint32_t)two;
+                    qv[i][s + 1] = (int32_t)(uint32_t)(two >> 32);
                 }
+#pragma unroll
+                for (int s = 0; s < kPopLook; ++s)
+                    if (p0[i] + s < hs[i] || p0[i] + s >= ts[i]) qv[i][s] = 0;
             }
-            hh = bh;
         }
-        else {
-            // the head entries themselves (0: pushed, not yet written); each
-            // lane keeps its best, then the wave's best
-            int qv[kScan];
+        // each entry's key (hl_sched.h), each lane's best, then the wave's
+        // best.  Preference for the workgroup's sub-queue, in wavefront steps
+        // of priority (one stream's column bands 30: +0.5 / +0.9 %,
+        // profiles/r06_ab_column_bands.log; several streams 12).
+        const bool oldest_first = P.hop < 0;
+        const int own = !oldest_first && lane % kSubQ == (int)(blockIdx.x % kSubQ) ? (S == 1 ? 30 : 12) : 0;
+        int kk[kScan][kPopLook];
+        int lbest = -1, bidx = 0;
 #pragma unroll
-            for (int i = 0; i < kScan; ++i) {
-                qv[i] = 0;
-                if (ins[i] && hs[i] < ts[i]) qv[i] = ld_relaxed(P.queue + ql[i] * nmb + hs[i]);
-            }
-            int key = -1, lh = 0, lq = 0, lfl = 0, lql = 0;
+        for (int i = 0; i < kScan; ++i) {
 #pragma unroll
-            for (int i = 0; i < kScan; ++i) {
-                if (qv[i] > 0) {
-                    const int a = qv[i] - 1, y = udiv_small(a, mbw, rc.mbw), x = a - y * mbw;
-                    // preference for the workgroup's sub-queue, in wavefront steps of priority (one stream's
-                    // column bands 30: +0.5 / +0.9 %, profiles/r06_ab_column_bands.log; several streams 12)
-                    const int own = sqs[i] == (int)(blockIdx.x % kSubQ) ? (S == 1 ? 30 : 12) : 0;
-                    const int kk = (((mbw - 1 - x) + 2 * (mbh - 1 - y) - P.hop * js[i] + own + 4096) << 6) | (63 - lane);
-                    if (kk > key) {
-                        key = kk;
-                        lh = hs[i];
-                        lq = qv[i];
-                        lfl = fl[i];
-                        lql = ql[i];
+            for (int s = 0; s < kPopLook; ++s) {
+                kk[i][s] = -1;
+                if (qv[i][s] > 0) {
+                    const int a = qv[i][s] - 1, y = udiv_small(a, mbw, rc.mbw), x = a - y * mbw;
+                    const int key = oldest_first ? sched_key_oldest((lane + 64 * i) / kSubQ) : sched_key(mbw, mbh, x, y, P.hop, js[i], own);
+                    kk[i][s] = sched_pack(key, lane);
+                    if (kk[i][s] > lbest) {
+                        lbest = kk[i][s];
+                        bidx = i * kPopLook + s;
                     }
                 }
+#if defined(HL_PROFILE)
+                pst[6] += __popcll(__ballot(qv[i][s] < 0));
+#endif
             }
-            for (int s2 = 1; s2 < 64; s2 <<= 1) key = max(key, __shfl_xor(key, s2, 64));
-            key = __builtin_amdgcn_readfirstlane(key);
-            if (key >= 0) {
-                i0 = 63 - (key & 63);
-                hh = __builtin_amdgcn_readlane(lh, i0);
-                v = __builtin_amdgcn_readlane(lq, i0);
-                bfl = __builtin_amdgcn_readlane(lfl, i0);
-                bql = __builtin_amdgcn_readlane(lql, i0);
-            }
-            // else: empty, or only pushes between their tail and slot stores
+            // taken slots at a head: move it past them (whoever sees them; a maximum)
+            // (no slot read: every word 0, the target is the head)
+            const int to = sched_head_target(hs[i], ts[i], p0[i], qv[i], kPopLook, -1);
+            if (to > hs[i]) sched_advance_head(P.head + ql[i], to);
+#if defined(HL_PROFILE)
+            pst[7] += __popcll(__ballot(to > hs[i]));
+#endif
         }
-        if (i0 >= 0) {
-            HL_POPSTAT(0);
-            const int f = bfl, qf = bql;
+        int wbest = lbest;
+        for (int s2 = 1; s2 < 64; s2 <<= 1) wbest = max(wbest, __shfl_xor(wbest, s2, 64));
+        wbest = __builtin_amdgcn_readfirstlane(wbest);
+        if (wbest >= 0) {  // else: empty, only taken slots, or only pushes between their tail and slot stores
+            // the lanes within the spread, the one this round tries, and in
+            // it (several candidates) one of its entries within the spread
+            const uint64_t within = __ballot(sched_within(lbest, wbest, kPopSpread));
+            const int m = sched_spread_count(within, poppers);
+            const int pick = __builtin_amdgcn_readfirstlane(sched_choose(within, sched_packed_lane(wbest), seq, poppers, stood_back >= kPopStandBack));
             int r = 0;
-            if (lane == 0 && atomicCAS(P.head + qf, hh, hh + 1) == hh) {
-                r = v;
-                // the slot is pushed right after the tail moved
-                for (unsigned k = 0; r == 0 && (r = ld_relaxed(P.queue + qf * nmb + hh)) == 0; ++k)
-                    if (k > (1u << 26)) {
-                        atomicAdd(P.err, 1);
-                        r = -1;
-                        break;
-                    }
-                if (r > 0 && atomicCAS(P.claim + f * nmb + r - 1, 0, 1) != 0) r = 0;
+            stood_back = pick < 0 ? stood_back + 1 : 0;
+            if (pick >= 0) HL_POPSTAT(0);
+            if (lane == pick) {
+                int ci = bidx;
+                if (m > 1) {
+                    int c = 0;
+#pragma unroll
+                    for (int i = 0; i < kScan; ++i)
+#pragma unroll
+                        for (int s = 0; s < kPopLook; ++s) c += sched_within(kk[i][s], wbest, kPopSpread) ? 1 : 0;
+                    int rth = sched_in_lane(seq, m, max(c, 1));
+#pragma unroll
+                    for (int i = 0; i < kScan; ++i)
+#pragma unroll
+                        for (int s = 0; s < kPopLook; ++s)
+                            if (sched_within(kk[i][s], wbest, kPopSpread) && rth-- == 0) ci = i * kPopLook + s;
+                }
+                int cv = 0, cpos = 0, cq = 0, cf = 0;
+#pragma unroll
+                for (int i = 0; i < kScan; ++i)
+#pragma unroll
+                    for (int s = 0; s < kPopLook; ++s)
+                        if (ci == i * kPopLook + s) {
+                            cv = qv[i][s];
+                            cpos = p0[i] + s;
+                            cq = ql[i];
+                            cf = fl[i];
+                        }
+                // the slot word itself, then the task's claim word (held by
+                // workgroup 0 already: the slot is spent, the attempt lost)
+                if (cv > 0 && sched_take_slot(P.queue + cq * nmb + cpos, cv)) {
+                    if (sched_claim_task(P.claim + cf * nmb + cv - 1)) r = cf * nmb + cv;  // task + 1
+#pragma unroll
+                    for (int i = 0; i < kScan; ++i)
+                        if (ci / kPopLook == i) {
+                            const int to = sched_head_target(hs[i], ts[i], p0[i], qv[i], kPopLook, cpos);
+                            if (to > hs[i]) sched_advance_head(P.head + ql[i], to);
+                        }
+                }
             }
-            r = __builtin_amdgcn_readfirstlane(r);
-            if (r < 0) return -1;
+            if (pick >= 0) r = __builtin_amdgcn_readlane(r, pick);
             if (r > 0) {
-                return f * nmb + r - 1;
+                HL_POPCYC(5);
+                HL_POP_RETURN(r - 1);
             }
-            HL_POPSTAT(1);
+            seq = sched_seq_next(seq);
+            if (pick >= 0) {
+                HL_POPSTAT(1);
+                HL_POPCYC(3);
+            }
             // another workgroup took it: retry, except beside a lone picture
             // (the 8x8 family's helpers on), where ~200 idle workgroups race for
             // each ready macroblock and the losers take a helper task instead
             // (in runs, measured: no gain, profiles/r06_ab_partitioning_helpers_in_runs.log)
-            if (!P.fam3 || P.nframes > 1) continue;
+            // (stood back: as a round that found nothing, below)
+            if (pick >= 0 && (!P.fam3 || P.nframes > 1)) continue;
         }
         if (P.helpers) {  // no macroblock ready: a helper task, unless its macroblock took it over
             // lane q reads FIFO q; the workgroup's own FIFO first, then the
@@ -505,17 +603,21 @@ __device__ int pop_task(const PipeArgs& P, int nmb, int mbw, int mbh, int& olc, 
                 }
                 r = __builtin_amdgcn_readfirstlane(r);
                 kind = __builtin_amdgcn_readfirstlane(kind);
-                if (r < 0) return -1;
+                if (r < 0) HL_POP_RETURN(-1);
                 if (r > 0) {
-                    return (1 + kind) * P.nframes * nmb + r - 1;  // intra helpers, then the 8x8 family's partitionings 3..6
+                    HL_POPCYC(5);
+                    HL_POP_RETURN((1 + kind) * P.nframes * nmb + r - 1);  // intra helpers, then the 8x8 family's partitionings 3..6
                 }
                 continue;
             }
         }
-        HL_POPSTAT(2);
+#if defined(HL_PROFILE)
+        const bool stood = wbest >= 0 && stood_back > 0;  // this round saw entries and made no attempt
+        ++pst[stood ? 8 : 2];
+#endif
         if (__builtin_amdgcn_s_memrealtime() - t0 > 1000000000ull) {  // 10 s at 100 MHz
             if (lane == 0) atomicAdd(P.err, 1);
-            return -1;
+            HL_POP_RETURN(-1);
         }
         // nothing ready: back off (fewer scans of the queue words while tasks run)
 #ifndef HL_IDLE_SLEEP
@@ -523,8 +625,13 @@ __device__ int pop_task(const PipeArgs& P, int nmb, int mbw, int mbh, int& olc, 
 #endif
         if (++empty < 4) __builtin_amdgcn_s_sleep(4);
         else __builtin_amdgcn_s_sleep(HL_IDLE_SLEEP);
+#if defined(HL_PROFILE)
+        HL_POPCYC(stood ? 9 : 4);
+#endif
     }
 }
+#undef HL_POP_RETURN
+#undef HL_POPCYC
 
 // Workgroup 0 claims tasks in run order (picture, then raster address)
 // instead of popping ready ones, and waits for the claimed task's
@@ -533,6 +640,14 @@ __device__ int pop_task(const PipeArgs& P, int nmb, int mbw, int mbh, int& olc, 
 // task is claimed, i.e. held by a running workgroup or done; so the earliest
 // unfinished task never waits, and the run completes with any number of
 // workgroups (one included) -- no geometry can deadlock.
+// pop_task adds no wait to this: a round reads words and issues at most one
+// slot CAS, one claim CAS and head maxima, none of which it repeats or polls
+// (a lost CAS ends the round; the next round reads everything again).  A
+// ready task is never hidden for good: its slot lies in [head, tail), the
+// head only moves past taken slots, and any round that sees taken slots at a
+// head moves it on, so the slot enters some popper's group after finitely
+// many rounds, and a popper stands back from a visible entry for at most
+// kPopStandBack rounds; and a task workgroup 0 holds needs no pop at all.
 __device__ int claim_next(const PipeArgs& P, int nmb, int& cursor)
 {
     const int lane = __lane_id(), total = P.nframes * nmb;
@@ -596,7 +711,8 @@ __global__ __launch_bounds__(kMbThreads, HL_PIPE_WAVES_PER_EU) void k_pipeline(P
     // per-workgroup totals (profiling build): prof[40..44] = waits for a ready
     // task, decisions, filters, tasks, workgroup lifetime (shader clock)
     unsigned long long pw_wait = 0, pw_mb = 0, pw_filt = 0, pw_n = 0, pw_hlp = 0, pw_hn = 0, pw_phlp = 0, pw_phn = 0;
-    unsigned long long pst[3] = {0, 0, 0};  // pop_task rounds (wave 0)
+    unsigned long long pst[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // pop_task rounds (wave 0)
+    unsigned long long pw_hwait = 0;  // pop time of the rounds that ended in a helper task
     unsigned long long ptail[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // after the filters: barrier, release fence, successors' release; early release; its fence, release, spin, acquire
     const unsigned long long pw_t0 = __builtin_readcyclecounter();
     unsigned long long* prof = P0.fr[0].F.prof;
@@ -701,6 +817,7 @@ __global__ __launch_bounds__(kMbThreads, HL_PIPE_WAVES_PER_EU) void k_pipeline(P
             }
 #if defined(HL_PROFILE)
             pw_hlp += __builtin_readcyclecounter() - pt1;
+            pw_hwait += pt1 - pt0;
             ++pw_hn;
             if (hk >= 2) {  // of which the 8x8 family's partitioning helpers
                 pw_phlp += __builtin_readcyclecounter() - pt1;
@@ -891,6 +1008,15 @@ __global__ __launch_bounds__(kMbThreads, HL_PIPE_WAVES_PER_EU) void k_pipeline(P
         atomicAdd(prof + 59, pw_phn);
         for (int i = 0; i < 3; ++i) atomicAdd(prof + 47 + i, pst[i]);  // pops: attempts, lost, empty rounds
         for (int i = 0; i < 8; ++i) atomicAdd(prof + 50 + i, ptail[i]);  // filters' barrier, release fence, successors, early release (fence, release, spin, acquire)
+        unsigned long long* pp = prof + 64 + 4 * nmb + kProfSites;  // the pop's words (kProfPop)
+        atomicAdd(pp + 0, pst[3]);  // cycles of lost, nothing-ready, winning and stood-back rounds
+        atomicAdd(pp + 1, pst[4]);
+        atomicAdd(pp + 2, pst[5]);
+        atomicAdd(pp + 3, pst[9]);
+        atomicAdd(pp + 4, pst[8]);  // rounds stood back, slots seen taken, head advances
+        atomicAdd(pp + 5, pst[6]);
+        atomicAdd(pp + 6, pst[7]);
+        atomicAdd(pp + 7, pw_hwait);
     }
 #endif
 }
@@ -938,11 +1064,7 @@ static int diag_count(int mbw, int rows, int diag)
 // encoder context
 // ---------------------------------------------------------------------------
 constexpr int kMaxRun = 128;  // pictures per pipelined launch and stream (bench.py MAX_RUN)
-#if defined(HL_PROFILE) && defined(HL_BAR_PROF) && HL_BAR_PROF >= 2
-constexpr int kProfExtra = 2 * kBarSites;  // per barrier site after the timeline (hl_mbcore.h)
-#else
-constexpr int kProfExtra = 0;
-#endif
+constexpr int kProfExtra = kProfSites + kProfPop;  // per barrier site after the timeline (hl_mbcore.h), then the pop's words
 constexpr int kRowsAt = 16;   // h_progress word of picture 0's row count
 
 // One picture's type and settings, decided as the reference does at the top of
@@ -1630,7 +1752,7 @@ static hipError_t ensure_sched(hl_amd_encoder_t* e, int slots)
     if ((r = hipMalloc(&e->d_pf, sizeof(PipeFrame) * slots)) || (r = hipHostMalloc(&e->h_pf, sizeof(PipeFrame) * slots, hipHostMallocDefault)) ||
         (r = hipMalloc(&e->d_cnt, sizeof(int32_t) * 2 * nmb * slots)) || (r = hipMalloc(&e->d_done, sizeof(int32_t) * nmb * slots)) ||
         (r = hipMalloc(&e->d_queue, sizeof(int32_t) * ((kSubQ + 5) * nmb * slots + kHelperQ))) ||
-        (r = hipMalloc(&e->d_head, sizeof(int32_t) * (2 * kSubQ * slots + kMaxStreams + 2 * kHelperQ))) ||
+        (r = hipMalloc(&e->d_head, sizeof(int32_t) * (2 * kSubQ * slots + kMaxStreams + 2 * kHelperQ + 1))) ||
         (r = hipMalloc(&e->d_hstate, sizeof(int32_t) * 5 * nmb * slots)) ||
         (r = hipMalloc(&e->d_f3, sizeof(Fam3Out) * 4 * nmb * (e->fam3 >= 2 ? slots : 1))))
         return r;
@@ -1915,6 +2037,7 @@ static int32_t encode_group(hl_amd_encoder_t* const* es, int S, int m, const uin
     P.hq_cap = (5 * slots * nmb + kHelperQ - 1) / kHelperQ;
     P.hq_head = e0->d_head + 2 * kSubQ * slots + kMaxStreams;
     P.hq_tail = e0->d_head + 2 * kSubQ * slots + kMaxStreams + kHelperQ;
+    P.poppers = e0->d_head + 2 * kSubQ * slots + kMaxStreams + 2 * kHelperQ;
     P.err = e0->d_err;
     static const bool trace = getenv("HL_AMD_TRACE_WRITERS") != nullptr;
     static unsigned long long* h_clock = nullptr;

@@ -42,6 +42,7 @@
 // before reading.  Every wait is bounded.
 #pragma once
 #include "hl_filters.h"
+#include "hl_sched.h"
 
 namespace hl {
 
@@ -184,7 +185,8 @@ struct PipeArgs {
     int32_t* cnt;    // [nframes][nmb] unfinished dependencies
     int32_t* claim;  // [nframes][nmb] 1 once a workgroup holds the task
     int32_t* done;   // [nframes][nmb] 1 once the task finished (reach_wait polls it)
-    int32_t* queue;  // [nframes][kSubQ][nmb] ready tasks, MB address + 1 (0 = slot not yet written)
+    int32_t* queue;  // [nframes][kSubQ][nmb] ready tasks: MB address a + 1, -(a + 1) once a popper took the slot (0 = slot not
+                     // yet written); a pop claims the slot word itself (hl_sched.h)
     // helper tasks (hl_mbcore.h intra_helper, guess_inter with f3out): a
     // ready P macroblock also queues its helpers, in kHelperQ FIFOs that
     // workgroups take from only when no macroblock is ready (ramp and tail of
@@ -202,9 +204,10 @@ struct PipeArgs {
     int32_t hq_cap;
     int32_t* hq_head;  // [kHelperQ]
     int32_t* hq_tail;  // [kHelperQ]
-    int32_t* head;   // [nframes][kSubQ] next queue slot to pop
+    int32_t* head;   // [nframes][kSubQ] a hint: every slot below it is taken; moved past taken slots by whoever sees them
     int32_t* tail;   // [nframes][kSubQ] next queue slot to push
     int32_t* oldest; // [nstreams] first unfinished picture of each stream
+    int32_t* poppers; // [1] workgroups inside pop_task (how far a pop spreads over the ready entries)
     int32_t* err;    // [0] number of bounded waits that gave up
     unsigned long long* pub_clock;  // diagnostics: device wall clock at each picture's publication, or null
 };

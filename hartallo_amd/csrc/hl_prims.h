@@ -445,6 +445,15 @@ __device__ __forceinline__ int32_t ld_relaxed(const int32_t* p)
 {
     return __hip_atomic_load((gi32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// two adjacent words in one load (8-byte aligned).  The words themselves are
+// written by 32-bit atomics: a mixed-size access C++ does not define.  It
+// relies on the hardware (an aligned 8-byte global load returns each dword
+// as some store left it); each half is only ever used as a hint that the
+// slot's own 32-bit CAS then confirms.
+__device__ __forceinline__ uint64_t ld_relaxed64(const uint64_t* p)
+{
+    return __hip_atomic_load((__attribute__((address_space(1))) uint64_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 __device__ __forceinline__ void st_relaxed(int32_t* p, int32_t v)
 {
     __hip_atomic_store((gi32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

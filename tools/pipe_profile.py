@@ -62,7 +62,15 @@ def main():
     ms = enc.timing_ms()
     nmb_ = nmb
     nsites = int(os.environ.get("HL_BAR_SITES", "0"))  # an HL_BAR_PROF=2 build: 2560 barrier sites after the timeline
-    cnt = enc.profile_counters(64 + 4 * nmb_ + 2 * nsites) if nsites else enc.profile_counters(64)
+    base = 64 + 4 * nmb_ + 2 * nsites  # the pop's eight words follow the timeline (and the barrier sites)
+    import ctypes
+    raw = (ctypes.c_ulonglong * (base + 8))()
+    if enc.lib.hl_amd_profile_counters(enc._h, raw, base + 8) == 0:
+        cnt = list(raw)
+        pop = cnt[base:base + 8]
+    else:  # a library from before the pop's words: it refuses the longer read
+        cnt = enc.profile_counters(base) if nsites else enc.profile_counters(64)
+        pop = None
     print(f"wg,R,window={geo}: {n} P pictures in {dt * 1e3:.1f} ms (kernel {ms[1]:.1f} ms, reruns {enc.last_reruns()}) helpers {enc.last_helper_stats()}")
     life, wait, mb, filt, tasks = cnt[44], cnt[40], cnt[41], cnt[42], cnt[43]
     if life:
@@ -71,7 +79,21 @@ def main():
               f" (~{life / wgs / (ms[1] * 1e-3) / 1e9:.2f} GHz shader clock if the kernel spans it)")
         hlp, hn = cnt[45], cnt[46]
         print(f"   pops: {cnt[47]} attempts on a macroblock ({cnt[47] / max(1, tasks):.2f} per task), {cnt[48]} lost to another "
-              f"workgroup, {cnt[49]} empty rounds ({cnt[49] / max(1, tasks):.1f} per task)")
+              f"workgroup ({100.0 * cnt[48] / max(1, cnt[47]):.1f} %), {cnt[49]} rounds with nothing ready ({cnt[49] / max(1, tasks):.1f} per task)")
+        hwait = 0
+        if pop:
+            # where a pop's time goes (cycles, back-off included): rounds lost to another workgroup, rounds that
+            # found nothing ready, rounds that stood back from entries they saw, the round that took a task
+            # (macroblock or helper); then the part of all that which ended in a helper task
+            lost, nothing, win, stood_c, stood_n, seen, moved, hwait = pop
+            inpop = lost + nothing + win + stood_c
+            print(f"   stood back: {stood_n} rounds ({stood_n / max(1, tasks):.1f} per task); slots seen taken {seen / max(1, tasks):.2f}, "
+                  f"head advances {moved / max(1, tasks):.2f} per task")
+            print(f"   inside pop_task: {100.0 * inpop / life:.1f} % of the workgroups' time ({inpop / max(1, tasks) / 1e3:.1f} kcycles/task): lost rounds "
+                  f"{100.0 * lost / life:.1f} %, nothing ready {100.0 * nothing / life:.1f} %, stood back {100.0 * stood_c / life:.1f} %, "
+                  f"winning round {100.0 * win / life:.1f} %")
+            print(f"   of the task-start waits below: {100.0 * wait / life:.1f} % ended in a macroblock (prof[40], all a library without the "
+                  f"pop's words reports), {100.0 * hwait / life:.1f} % in a helper task")
         if hn:
             print(f"   helper tasks {hn} ({hn / max(1, n * nmb):.2f} per MB), {hlp / hn / 1e3:.1f} kcycles each")
         if cnt[59]:
@@ -82,8 +104,9 @@ def main():
               f"successors {cnt[52] / max(1, tasks) / 1e3:.1f} kcycles/task; early release block (in the filters) {cnt[53] / max(1, tasks) / 1e3:.1f} "
               f"(fence {cnt[54] / max(1, tasks) / 1e3:.1f}, release {cnt[55] / max(1, tasks) / 1e3:.1f}, spin {cnt[56] / max(1, tasks) / 1e3:.1f}, "
               f"acquire {cnt[57] / max(1, tasks) / 1e3:.1f})")
-        for name, v in (("task-start waits", wait), ("decisions", mb), ("deblock + planes", filt), ("intra helpers", hlp),
-                        ("rest", life - wait - mb - filt - hlp)):
+        # task-start waits: pop, acquire and barrier of every task start, macroblock or helper
+        for name, v in (("task-start waits", wait + hwait), ("decisions", mb), ("deblock + planes", filt), ("intra helpers", hlp),
+                        ("rest", life - wait - hwait - mb - filt - hlp)):
             print(f"   {name:18s} {100.0 * v / life:6.1f} %   {v / max(1, tasks) / 1e3:9.1f} kcycles/task")
     default_build = not any(os.environ.get(k) for k in ("HL_I4_NAMES", "HL_STEP_NAMES"))
     if default_build and cnt[25]:  # slot 12 of the default profiling build: wave 0's evaluation passes / those whose quads all hit the memo
