@@ -4,6 +4,7 @@
 #   tests/emu/libhl_pyr_emu.so       test-only host build of the layer pyramid (hl_pyramid.h)
 #   tests/emu/libhl_scene_emu.so     test-only host build of the scene-cut analysis (hl_scene.h)
 #   tests/emu/libhl_quality_emu.so   test-only host build of the quality metric (hl_quality.h)
+#   tests/emu/libhl_ingest_emu.so    test-only host build of the frame ingest (hl_ingest.h)
 #   tests/emu/libhl_sched_emu.so     test-only host build of the pipelined run's pop (hl_sched.h)
 #   tests/emu/libhl_rec_emu.so       test-only host exports of the candidate record's pack / unpack (hl_mbcore.h)
 #   tests/gpu_unit/libhl_unit.so     test-only GPU unit kernels (coop pipeline vs scalar primitives)
@@ -25,16 +26,23 @@ CXXFLAGS := -std=c++17 -O3 -fPIC -ffp-contract=off -Wall -Wno-unused-function -W
 # the latency-bound macroblock decision (1088p bench +1.5 %, bit-exact;
 # profiles/r02_sched_strategy_ab.log)
 DEVFLAGS := -mllvm -amdgpu-sched-strategy=iterative-ilp
+# k_ingest (hl_ingest.hip) is compiled on its own, without DEVFLAGS: that
+# strategy crashes the compiler's register allocator on the planar-RGB kernel
+INGOBJ  := build/obj/hl_ingest.o
 
 .PHONY: all product emu unit oracle profile poison variant sanitize ubsan clean
 all: product emu unit oracle sanitize
 
 product: hartallo_amd/libhartallo_amd.so
-emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so
+emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so
 unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so
 
-hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -shared -o $@ $(KSRC) $(HOSTSRC)
+$(INGOBJ): $(CSRC)/hl_ingest.hip $(CSRC)/hl_ingest.h
+	mkdir -p build/obj
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c -o $@ $(CSRC)/hl_ingest.hip
+
+hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS) $(INGOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -shared -o $@ $(KSRC) $(HOSTSRC) -x none $(INGOBJ)
 
 # (hl_emu_search.hip = hl_emu_ctl.hip plus the search table's export;
 # hl_emu_ctl.hip = hl_emu_memo.hip plus emu_encode_frame_ex; hl_emu_memo.hip =
@@ -55,6 +63,10 @@ tests/emu/libhl_scene_emu.so: tests/emu/hl_scene_emu.cpp $(CSRC)/hl_scene.h
 # the quality metric's staging, per-strip and per-window code on the host (no device code)
 tests/emu/libhl_quality_emu.so: tests/emu/hl_quality_emu.cpp $(CSRC)/hl_quality.h
 	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_quality_emu.cpp
+
+# the frame ingest's per-tile code on the host (no device code)
+tests/emu/libhl_ingest_emu.so: tests/emu/hl_ingest_emu.cpp $(CSRC)/hl_ingest.h
+	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_ingest_emu.cpp
 
 # the pop's key, choice, head rule and slot / claim transitions on the host (no device code)
 tests/emu/libhl_sched_emu.so: tests/emu/hl_sched_emu.cpp $(CSRC)/hl_sched.h
@@ -82,11 +94,15 @@ tests/gpu_unit/libhl_unit_rec.so: tests/gpu_unit/hl_unit_rec.hip $(HDRS)
 #       (hl_writer.h RowGate) under ThreadSanitizer
 #   tests/sanitize/pop_tsan  the pipelined run's pop protocol (hl_sched.h with
 #       task_deps / task_succ) on 16 threads under ThreadSanitizer
+#   tests/sanitize/ingest_asan  the frame ingest's per-tile code (hl_ingest.h)
+#       over exactly-sized heap buffers under AddressSanitizer +
+#       UndefinedBehaviorSanitizer (plain C++; like the two above, the
+#       program carries the sanitizers' runtimes itself)
 # (hipcc: every -fsanitize= directly after -Xarch_host, host code only)
 SANFLAGS := -std=c++17 -O1 -g -fno-omit-frame-pointer -fPIC -ffp-contract=off -Wno-unused-function -Wno-unused-variable
 ASAN := -Xarch_host -fsanitize=address
 UBSAN := -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined
-sanitize: tests/sanitize/libhl_emu_asan.so tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan
+sanitize: tests/sanitize/libhl_emu_asan.so tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan
 tests/sanitize/hl_writer_asan.o: $(CSRC)/hl_writer.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) $(ASAN) $(UBSAN) -c -o $@ $<
 tests/sanitize/hl_rc_asan.o: $(CSRC)/hl_rc.cpp $(HDRS)
@@ -99,6 +115,8 @@ tests/sanitize/rowgate_tsan: tests/sanitize/rowgate_tsan.cpp $(CSRC)/hl_writer.c
 	$(HIPCC) $(SANFLAGS) -Xarch_host -fsanitize=thread -o $@ tests/sanitize/rowgate_tsan.cpp $(CSRC)/hl_writer.cpp -lpthread
 tests/sanitize/pop_tsan: tests/sanitize/pop_tsan.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) -Xarch_host -fsanitize=thread -o $@ -x hip tests/sanitize/pop_tsan.cpp -lpthread
+tests/sanitize/ingest_asan: tests/sanitize/ingest_asan.cpp $(CSRC)/hl_ingest.h
+	$(HIPCC) $(SANFLAGS) $(ASAN) $(UBSAN) -o $@ -x c++ tests/sanitize/ingest_asan.cpp
 # the emulator under UndefinedBehaviorSanitizer too: a 16-minute compile of
 # the kernel logic, run once per change of the shift / overflow idioms
 # (DESIGN.md §2); tests/test_sanitizers.py uses it when it is present
@@ -109,31 +127,31 @@ tests/sanitize/libhl_emu_ubsan.so: $(EMUSRC) $(EMUINC) $(HOSTSRC) $(HDRS)
 # profiling build: same library (same device scheduling flags) with per-phase
 # clock64 counters (tools/phase_profile.py)
 profile: build/prof/hartallo_amd/libhartallo_amd.so
-build/prof/hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
+build/prof/hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS) $(INGOBJ)
 	mkdir -p build/prof/hartallo_amd
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -DHL_PROFILE=1 -shared -o $@ $(KSRC) $(HOSTSRC)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -DHL_PROFILE=1 -shared -o $@ $(KSRC) $(HOSTSRC) -x none $(INGOBJ)
 
 # debug builds: LDS poisoned before every macroblock with two different salts
 # (tools/gpu_diag.sh); any output difference names a read of uninitialised LDS
 poison: build/poison1/libhartallo_amd.so build/poison2/libhartallo_amd.so
-build/poison%/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
+build/poison%/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS) $(INGOBJ)
 	mkdir -p build/poison$*
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -DHL_POISON_LDS=$* -shared -o $@ $(KSRC) $(HOSTSRC)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -DHL_POISON_LDS=$* -shared -o $@ $(KSRC) $(HOSTSRC) -x none $(INGOBJ)
 
 # memory-scope variants of the pipelined run's fences (diagnostics)
 scopes: build/acqsys/libhartallo_amd.so build/relacqsys/libhartallo_amd.so
-build/acqsys/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
+build/acqsys/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS) $(INGOBJ)
 	mkdir -p build/acqsys
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) '-DHL_ACQ_SCOPE=""' -shared -o $@ $(KSRC) $(HOSTSRC)
-build/relacqsys/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) '-DHL_ACQ_SCOPE=""' -shared -o $@ $(KSRC) $(HOSTSRC) -x none $(INGOBJ)
+build/relacqsys/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS) $(INGOBJ)
 	mkdir -p build/relacqsys
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) '-DHL_ACQ_SCOPE=""' '-DHL_REL_SCOPE=""' -shared -o $@ $(KSRC) $(HOSTSRC)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) '-DHL_ACQ_SCOPE=""' '-DHL_REL_SCOPE=""' -shared -o $@ $(KSRC) $(HOSTSRC) -x none $(INGOBJ)
 
 # variants of the product for A/B runs: make variant V=<name> VDEFS="-D..."
 variant: build/$(V)/libhartallo_amd.so
-build/$(V)/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS)
+build/$(V)/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS) $(INGOBJ)
 	mkdir -p build/$(V)
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) $(VDEFS) -shared -o $@ $(KSRC) $(HOSTSRC)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) $(VDEFS) -shared -o $@ $(KSRC) $(HOSTSRC) -x none $(INGOBJ)
 
 # (then the drivers with a per-frame schedule, tests/refdrive, where the reference library was built)
 oracle: product  # oracle/_ref/drop_in_enc links the product library
@@ -141,5 +159,5 @@ oracle: product  # oracle/_ref/drop_in_enc links the product library
 	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
-	rm -f hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan
+	rm -f $(INGOBJ) hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan
 	$(MAKE) -C oracle clean

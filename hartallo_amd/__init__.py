@@ -5,14 +5,17 @@ hand-written HIP kernels, and its spatial-SVC enhancement layers, bit-exact
 with the reference encoder, behind a
 C ABI (include/hartallo_amd.h) that a hartallo plugin forwards to.
 """
-from ._lib import (EXPORTED_SYMBOLS, HL_AMD_RESULT_TYPE_DATA, HL_AMD_RESULT_TYPE_HDR, LIB_PATH, EncodeResult, Encoder,
-                   FrameCtl, HlAmdError, Quality, SvcEncoder, load_library, psnr_db, ssim_mean)
+from ._lib import (EXPORTED_SYMBOLS, HL_AMD_FORMAT_I420, HL_AMD_FORMAT_NV12, HL_AMD_FORMAT_RGB24, HL_AMD_FORMAT_RGBA32,
+                   HL_AMD_FORMAT_RGBP, HL_AMD_MATRIX_BT601, HL_AMD_MATRIX_BT709, HL_AMD_RANGE_FULL, HL_AMD_RANGE_LIMITED,
+                   HL_AMD_RESULT_TYPE_DATA, HL_AMD_RESULT_TYPE_HDR, LIB_PATH, EncodeResult, Encoder, Frame, FrameCtl, HlAmdError,
+                   Quality, SvcEncoder, load_library, psnr_db, ssim_mean)
 
 __all__ = [
     "Encoder",
     "SvcEncoder",
     "EncodeResult",
     "FrameCtl",
+    "Frame",
     "HlAmdError",
     "load_library",
     "Quality",
@@ -22,4 +25,13 @@ __all__ = [
     "EXPORTED_SYMBOLS",
     "HL_AMD_RESULT_TYPE_DATA",
     "HL_AMD_RESULT_TYPE_HDR",
+    "HL_AMD_FORMAT_I420",
+    "HL_AMD_FORMAT_NV12",
+    "HL_AMD_FORMAT_RGB24",
+    "HL_AMD_FORMAT_RGBA32",
+    "HL_AMD_FORMAT_RGBP",
+    "HL_AMD_MATRIX_BT601",
+    "HL_AMD_MATRIX_BT709",
+    "HL_AMD_RANGE_LIMITED",
+    "HL_AMD_RANGE_FULL",
 ]

@@ -32,6 +32,16 @@ HL_AMD_ENCODING_INTRA = 1
 HL_AMD_ENCODING_INTER = 2
 HL_AMD_ENCODING_LOSSLESS = 3
 HL_AMD_ENCODING_RAW = 4
+# HL_AMD_FORMAT_*, HL_AMD_MATRIX_*, HL_AMD_RANGE_* (hl_amd_frame_t, hl_amd_set_colour)
+HL_AMD_FORMAT_I420 = 0
+HL_AMD_FORMAT_NV12 = 1
+HL_AMD_FORMAT_RGB24 = 2
+HL_AMD_FORMAT_RGBA32 = 3
+HL_AMD_FORMAT_RGBP = 4
+HL_AMD_MATRIX_BT601 = 0
+HL_AMD_MATRIX_BT709 = 1
+HL_AMD_RANGE_LIMITED = 0
+HL_AMD_RANGE_FULL = 1
 
 # every symbol include/hartallo_amd.h declares
 EXPORTED_SYMBOLS = (
@@ -97,6 +107,11 @@ EXPORTED_SYMBOLS = (
     "hl_amd_bench_quality",
     "hl_amd_psnr_db",
     "hl_amd_ssim_mean",
+    "hl_amd_set_colour",
+    "hl_amd_encode_frame",
+    "hl_amd_encode_frames",
+    "hl_amd_get_input",
+    "hl_amd_bench_ingest",
     "hl_amd_version",
 )
 
@@ -149,6 +164,124 @@ def _ctl_array(ctls, n):
     if len(ctls) != n:
         raise HlAmdError(HL_AMD_ERROR_INVALID_PARAMETER, "ctl (one per frame)")
     return (_FrameCtl * n)(*[c._c() for c in ctls])
+
+
+class _Frame(ctypes.Structure):
+    _fields_ = [("format", ctypes.c_int32), ("on_device", ctypes.c_int32), ("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
+
+
+_FRAME_PLANES = {HL_AMD_FORMAT_I420: 3, HL_AMD_FORMAT_NV12: 2, HL_AMD_FORMAT_RGB24: 1, HL_AMD_FORMAT_RGBA32: 1, HL_AMD_FORMAT_RGBP: 3}
+
+
+def _array_view(a):
+    """(address, shape, strides in bytes, on_device) of a numpy uint8 array or
+    of an object with data_ptr(), stride(), shape and is_cuda (a torch
+    tensor); ValueError for anything else and for another element type."""
+    if hasattr(a, "data_ptr") and hasattr(a, "stride") and hasattr(a, "is_cuda"):
+        if getattr(a, "element_size", lambda: 1)() != 1 or "uint8" not in str(getattr(a, "dtype", "uint8")):
+            raise ValueError("frames are uint8")
+        return int(a.data_ptr()), tuple(int(d) for d in a.shape), tuple(int(x) for x in a.stride()), bool(a.is_cuda)
+    import numpy as np
+
+    if not isinstance(a, np.ndarray):
+        raise ValueError("a numpy array or a tensor with data_ptr(), stride(), shape and is_cuda")
+    if a.dtype != np.uint8:
+        raise ValueError("frames are uint8")
+    return int(a.ctypes.data), tuple(a.shape), tuple(int(x) for x in a.strides), False
+
+
+def _plane_2d(a, width_bytes=None):
+    """A plane of rows: (address, rows, row bytes, pitch, on_device); the
+    samples of a row must be dense and the pitch positive."""
+    ptr, shape, st, dev = _array_view(a)
+    if len(shape) != 2 or st[1] != 1 or st[0] < shape[1]:
+        raise ValueError("a plane is (rows, bytes) with dense rows and a pitch of at least the row")
+    if width_bytes is not None and shape[1] != width_bytes:
+        raise ValueError("plane width")
+    return ptr, shape[0], shape[1], st[0], dev
+
+
+@dataclass
+class Frame:
+    """hl_amd_frame_t: a frame by its format (HL_AMD_FORMAT_*), the addresses
+    of its planes, the bytes between their rows (0 = dense) and whether the
+    planes are in device memory.  `source` keeps what the addresses point into
+    alive; width and height (when known) are checked against the encoder's."""
+
+    format: int
+    planes: tuple
+    pitches: tuple = (0, 0, 0)
+    on_device: bool = False
+    source: object = None
+    width: int = 0
+    height: int = 0
+
+    def __post_init__(self):
+        if self.format not in _FRAME_PLANES:
+            raise ValueError("format: one of HL_AMD_FORMAT_*")
+        self.planes = tuple(int(p) for p in self.planes)
+        self.pitches = tuple(int(p) for p in self.pitches)
+        n = _FRAME_PLANES[self.format]
+        if len(self.planes) < n or len(self.pitches) < n:
+            raise ValueError(f"format {self.format} has {n} planes")
+
+    def _c(self) -> _Frame:
+        f = _Frame()
+        f.format, f.on_device = self.format, 1 if self.on_device else 0
+        for c in range(min(3, len(self.planes), len(self.pitches))):
+            f.plane[c] = self.planes[c] or None
+            f.pitch[c] = self.pitches[c]
+        return f
+
+    @classmethod
+    def from_array(cls, a, format=None) -> "Frame":
+        """An RGB frame from a numpy uint8 array or a uint8 tensor (anything
+        with data_ptr(), stride(), shape and is_cuda), which may be a strided
+        view: (H, W, 3) is RGB24 and (H, W, 4) RGBA32 -- dimensions 1 and 2
+        dense, the pitch is stride 0 -- and (3, H, W) is RGBP with a pitch per
+        channel from stride 1.  ValueError for what the descriptor cannot
+        express."""
+        ptr, shape, st, dev = _array_view(a)
+        if len(shape) != 3:
+            raise ValueError("(H, W, 3), (H, W, 4) or (3, H, W); I420 and NV12 have their own constructors")
+        if format is None:
+            if shape[2] in (3, 4) and shape[0] != 3:
+                format = HL_AMD_FORMAT_RGB24 if shape[2] == 3 else HL_AMD_FORMAT_RGBA32
+            elif shape[0] == 3:
+                format = HL_AMD_FORMAT_RGBP
+            else:
+                raise ValueError("neither (H, W, 3 or 4) nor (3, H, W)")
+        if format in (HL_AMD_FORMAT_RGB24, HL_AMD_FORMAT_RGBA32):
+            ch = 3 if format == HL_AMD_FORMAT_RGB24 else 4
+            h, w = shape[0], shape[1]
+            if shape[2] != ch or st[2] != 1 or st[1] != ch or (h > 1 and st[0] < w * ch):
+                raise ValueError("packed RGB needs dense samples and rows (strides (pitch, channels, 1))")
+            return cls(format, (ptr,), (st[0] if h > 1 else 0,), dev, a, w, h)
+        if format == HL_AMD_FORMAT_RGBP:
+            h, w = shape[1], shape[2]
+            if shape[0] != 3 or st[2] != 1 or (h > 1 and st[1] < w) or st[0] < 0:
+                raise ValueError("planar RGB needs dense rows (strides (plane, pitch, 1))")
+            return cls(format, tuple(ptr + c * st[0] for c in range(3)), (st[1] if h > 1 else 0,) * 3, dev, a, w, h)
+        raise ValueError("from_array makes RGB frames; I420 and NV12 have their own constructors")
+
+    @classmethod
+    def i420(cls, y, u, v) -> "Frame":
+        """Planar 4:2:0 from three (rows, samples) planes, each with its own pitch."""
+        py, h, w, sy, dy = _plane_2d(y)
+        pu, hu, wu, su, du = _plane_2d(u, w // 2)
+        pv, hv, wv, sv, dv = _plane_2d(v, w // 2)
+        if hu != h // 2 or hv != h // 2 or not dy == du == dv:
+            raise ValueError("I420: chroma planes of half the size, all on the same side")
+        return cls(HL_AMD_FORMAT_I420, (py, pu, pv), (sy, su, sv), dy, (y, u, v), w, h)
+
+    @classmethod
+    def nv12(cls, y, uv) -> "Frame":
+        """NV12 from a (H, W) luma plane and a (H / 2, W) plane of U, V pairs."""
+        py, h, w, sy, dy = _plane_2d(y)
+        pc, hc, wc, sc, dc = _plane_2d(uv, w)
+        if hc != h // 2 or dy != dc:
+            raise ValueError("NV12: an interleaved chroma plane of half the rows, on the same side")
+        return cls(HL_AMD_FORMAT_NV12, (py, pc), (sy, sc), dy, (y, uv), w, h)
 
 
 def _mb_record_dtype():
@@ -345,6 +478,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
             getattr(lib, name).restype = ctypes.c_double
+    pf = ctypes.POINTER(_Frame)
+    for name, args in (("hl_amd_set_colour", [vp, i32, i32]), ("hl_amd_encode_frame", [vp, pf, pc, ctypes.POINTER(_Result)]),
+                       ("hl_amd_encode_frames", [vp, i32, pf, pc, ctypes.POINTER(_Result)]),
+                       ("hl_amd_get_input", [vp, i32, vp, vp, vp]), ("hl_amd_bench_ingest", [vp, i32, ctypes.POINTER(ctypes.c_float)])):
+        if hasattr(lib, name):  # (absent from builds before the frame ingest loaded through HL_LIB)
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = i32
     lib.hl_amd_svc_layer_ms.argtypes = [vp]
     lib.hl_amd_svc_layer_ms.restype = ctypes.c_float
     lib.hl_amd_version.argtypes = []
@@ -604,6 +744,66 @@ class Encoder:
         rc = self.lib.hl_amd_bench_quality(self._h, iters, ctypes.byref(ms))
         if rc:
             raise HlAmdError(rc, "hl_amd_bench_quality")
+        return ms.value
+
+    def set_colour(self, matrix: int = HL_AMD_MATRIX_BT601, range: int = HL_AMD_RANGE_LIMITED) -> None:
+        """The matrix and range RGB frames are converted with from now on
+        (hl_amd_set_colour); the default is BT.601 limited."""
+        rc = self.lib.hl_amd_set_colour(self._h, matrix, range)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_set_colour")
+
+    def _check_frame(self, f: "Frame"):
+        if f.width and (f.width, f.height) != (self.width, self.height):
+            raise HlAmdError(HL_AMD_ERROR_INVALID_FORMAT, "frame (picture size)")
+
+    def encode_frame(self, frame: "Frame", ctl: "FrameCtl | None" = None) -> EncodeResult:
+        """One frame by its description -- pitched I420, NV12, RGB24, RGBA32
+        or planar RGB, on the host or in device memory -- converted on the GPU
+        and coded as encode / encode_device code a frame (hl_amd_encode_frame)."""
+        self._check_frame(frame)
+        r = _Result()
+        c = frame._c()
+        rc = self.lib.hl_amd_encode_frame(self._h, ctypes.byref(c), ctypes.byref(ctl._c()) if ctl is not None else None, ctypes.byref(r))
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_frame")
+        return self._result(r)
+
+    def encode_frames_device(self, frames, ctl=None, collect: bool = True):
+        """Consecutive frames in device memory by their descriptions, converted
+        on the GPU and coded as encode_batch_device codes frames
+        (hl_amd_encode_frames); one result per frame."""
+        n = len(frames)
+        for f in frames:
+            self._check_frame(f)
+        arr = (_Frame * n)(*[f._c() for f in frames])
+        res = (_Result * n)()
+        rc = self.lib.hl_amd_encode_frames(self._h, n, arr, _ctl_array(ctl, n), res)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_frames")
+        self._last_batch = res
+        return [self._result(r) for r in res] if collect else sum(r.data_size for r in res)
+
+    def last_input(self, k: int = 0):
+        """The dense planes (y, u, v) picture k of the last encode_frame /
+        encode_frames_device call was coded from (hl_amd_get_input)."""
+        import numpy as np
+
+        y = np.empty((self.height, self.width), np.uint8)
+        u = np.empty((self.height // 2, self.width // 2), np.uint8)
+        v = np.empty_like(u)
+        rc = self.lib.hl_amd_get_input(self._h, k, y.ctypes.data, u.ctypes.data, v.ctypes.data)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_get_input")
+        return y, u, v
+
+    def bench_ingest(self, iters: int = 50) -> float:
+        """average ms of the k_ingest launch(es) of the last frame call, whose
+        frames must still be there (diagnostics)"""
+        ms = ctypes.c_float()
+        rc = self.lib.hl_amd_bench_ingest(self._h, iters, ctypes.byref(ms))
+        if rc:
+            raise HlAmdError(rc, "hl_amd_bench_ingest")
         return ms.value
 
     def bench_planes(self, iters: int = 50) -> float:

@@ -13,6 +13,7 @@
 // Runs of pictures: k_pipeline (hl_pipeline.h), one persistent launch.
 // Spatial SVC layers: k_svc_mb, k_deblock_rows, k_el_count / k_el_write; the
 // lower layers' input from the top layer's frame: k_pyramid (hl_pyramid.h).
+// Frames that are not dense I420 (hl_amd_encode_frame): k_ingest (hl_ingest.h).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,6 +39,7 @@
 #include "hl_pyramid.h"
 #include "hl_scene.h"
 #include "hl_quality.h"
+#include "hl_ingest.h"
 #include "hl_writer.h"
 #endif
 
@@ -1218,6 +1220,26 @@ struct hl_amd_encoder_s {
     const uint8_t** h_q_tab = nullptr;           // ... staged (pinned)
     std::vector<char> q_valid[4];                // per layer and picture of the last call: measured
     int q_last_m = 0, q_last_slot = 0;           // the last AVC launch (hl_amd_bench_quality)
+    // frame ingest (hl_amd_encode_frame / hl_amd_encode_frames, hl_ingest.h):
+    // what is not a dense I420 device frame is converted by k_ingest on the
+    // encoder's stream into d_in, a look-ahead slot or d_inb before the call
+    // is coded from those planes
+    int32_t in_matrix = 0, in_range = 0;         // hl_amd_set_colour
+    uint8_t* d_stage = nullptr;                  // a host frame's rows, plane by plane, dense (256-byte aligned planes)
+    size_t stage_cap = 0;
+    uint8_t* d_inb = nullptr;                    // hl_amd_encode_frames: the converted frames, Y | U | V each
+    size_t inb_cap = 0;
+    hl::InFrame* d_in_tab = nullptr;             // ... and their descriptions, format by format
+    size_t in_tab_cap = 0;
+    std::vector<hl::InFrame> in_tab;             // ... staged
+    struct InLaunch {
+        hl::InArgs A;
+        int fmt, frames;
+    };
+    std::vector<InLaunch> in_launches;           // the last frame call's launches (hl_amd_bench_ingest)
+    std::vector<const uint8_t*> in_src;          // [3 k + c] the converted planes of its picture k, null: forwarded
+    bool in_ok = false;                          // the last encode call was a frame call and ended well
+    bool in_nested = false;                      // inside a frame call (encode_pictures keeps the above)
 };
 
 static void svc_free(hl_amd_encoder_t* e);
@@ -1253,6 +1275,9 @@ static void free_all(hl_amd_encoder_t* e)
     for (int l = 0; l < 4; ++l) (void)hipFree(e->d_q_mb[l]);
     (void)hipFree(e->d_q_tab);
     (void)hipHostFree(e->h_q_tab);
+    (void)hipFree(e->d_stage);
+    (void)hipFree(e->d_inb);
+    (void)hipFree(e->d_in_tab);
     (void)hipFree(e->d_bpic);
     (void)hipFree(e->d_bpl);
     (void)hipFree(e->d_brec);
@@ -2413,6 +2438,7 @@ static int32_t encode_pictures(hl_amd_encoder_t* e, int n, const uint8_t* const*
                                hl_amd_result_t* results, const hl_amd_frame_ctl_t* ctl = nullptr)
 {
     if (!e->q_nested) quality_drop(e);  // a refused or failed call leaves no results
+    if (!e->in_nested) e->in_ok = false;  // not a frame call: hl_amd_get_input has nothing to show
     if (e->broken) return HL_AMD_ERROR_INVALID_STATE;
     for (int i = 0; i < n; ++i)
         if (!quality_aligned(e, y[i], u[i], v[i])) return HL_AMD_ERROR_INVALID_PARAMETER;
@@ -2458,6 +2484,7 @@ extern "C" int32_t hl_amd_encode_streams_ex(hl_amd_encoder_t* const* encoders, i
         if (e->rc || e->svc || e->broken) return HL_AMD_ERROR_INVALID_STATE;
     }
     for (int s = 0; s < count; ++s) quality_drop(encoders[s]);  // a refused or failed call leaves no results
+    for (int s = 0; s < count; ++s) encoders[s]->in_ok = false;  // (not a frame call)
     for (int s = 0; s < count && ctl; ++s) {
         const int32_t rc = check_ctl(encoders[s], ctl + (size_t)s * n, n);
         if (rc) return rc;
@@ -2912,6 +2939,274 @@ extern "C" int32_t hl_amd_encode_ex(hl_amd_encoder_t* e, const uint8_t* y, const
     HL_HIP_CHECK(hipMemcpyAsync(e->d_in[2], v, (size_t)e->Wc * e->Hc, hipMemcpyHostToDevice, e->stream));
     const uint8_t *dy = e->d_in[0], *du = e->d_in[1], *dv = e->d_in[2];
     return encode_pictures(e, 1, &dy, &du, &dv, r, ctl);
+}
+
+// ---------------------------------------------------------------------------
+// Frame ingest (hl_amd_encode_frame / hl_amd_encode_frames; no reference
+// interface: hl_frame_video_t has neither a pitch nor a format).  k_ingest
+// (hl_ingest.h) writes dense I420 planes on the encoder's stream -- one launch
+// per call and format -- and the call is then coded from those planes by
+// encode_pictures or the look-ahead queue: every rule is theirs.
+// ---------------------------------------------------------------------------
+// a dense I420 frame in device memory: coded from the caller's planes as it is
+static bool in_forwarded(const hl_amd_encoder_t* e, const hl_amd_frame_t& f)
+{
+    if (!f.on_device || f.format != HL_AMD_FORMAT_I420) return false;
+    for (int c = 0; c < 3; ++c)
+        if (f.pitch[c] && f.pitch[c] != in_row_bytes(IN_I420, c, e->W)) return false;
+    return true;
+}
+
+// every frame of a call, before anything is uploaded, converted or queued (include/hartallo_amd.h)
+static int32_t check_frames(const hl_amd_encoder_t* e, const hl_amd_frame_t* f, int n, bool device_only)
+{
+    const bool queued = !device_only && e->lookahead > 1;  // hl_amd_encode_frame with look-ahead: coded from the queue's copy
+    for (int i = 0; i < n; ++i) {
+        if (f[i].format < 0 || f[i].format >= IN_FORMATS) return HL_AMD_ERROR_INVALID_PARAMETER;
+        if (device_only && !f[i].on_device) return HL_AMD_ERROR_INVALID_PARAMETER;
+        for (int c = 0; c < in_planes(f[i].format); ++c)
+            if (!f[i].plane[c] || f[i].pitch[c] < 0 || (f[i].pitch[c] && f[i].pitch[c] < in_row_bytes(f[i].format, c, e->W)))
+                return HL_AMD_ERROR_INVALID_PARAMETER;
+        if (in_forwarded(e, f[i])) {  // the caller's planes are what scene-cut detection and quality read, unless the frame is queued
+            if (!queued && (!quality_aligned(e, f[i].plane[0], f[i].plane[1], f[i].plane[2]) || (e->sc_thr && ((uintptr_t)f[i].plane[0] & 3))))
+                return HL_AMD_ERROR_INVALID_PARAMETER;
+        }
+        else if (f[i].on_device) {  // k_ingest loads 4-byte words
+            for (int c = 0; c < in_planes(f[i].format); ++c)
+                if (((uintptr_t)f[i].plane[c] | (uint64_t)f[i].pitch[c]) & 3) return HL_AMD_ERROR_INVALID_PARAMETER;
+        }
+    }
+    return HL_AMD_SUCCESS;
+}
+
+// a (checked) device frame as k_ingest takes it; dst stays to be set
+static InFrame in_describe(const hl_amd_encoder_t* e, const hl_amd_frame_t& f)
+{
+    InFrame F{};
+    for (int c = 0; c < in_planes(f.format); ++c) {
+        F.plane[c] = f.plane[c];
+        F.pitch[c] = f.pitch[c] ? f.pitch[c] : in_row_bytes(f.format, c, e->W);
+    }
+    return F;
+}
+
+// a (checked) host frame's rows into d_stage, plane by plane and dense: padding is not read
+static int32_t in_stage(hl_amd_encoder_t* e, const hl_amd_frame_t& f, InFrame* S)
+{
+    size_t at[3] = {}, total = 0;
+    for (int c = 0; c < in_planes(f.format); ++c) {
+        at[c] = total;
+        total += ((size_t)in_row_bytes(f.format, c, e->W) * in_rows(f.format, c, e->H) + 255) & ~(size_t)255;
+    }
+    if (e->stage_cap < total) {
+        (void)hipFree(e->d_stage);
+        e->d_stage = nullptr;
+        e->stage_cap = 0;
+        if (hipMalloc(&e->d_stage, total) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e->stage_cap = total;
+    }
+    for (int c = 0; c < in_planes(f.format); ++c) {
+        const size_t rb = (size_t)in_row_bytes(f.format, c, e->W), rows = (size_t)in_rows(f.format, c, e->H);
+        const size_t pitch = f.pitch[c] ? (size_t)f.pitch[c] : rb;
+        if (pitch == rb) HL_HIP_CHECK(hipMemcpyAsync(e->d_stage + at[c], f.plane[c], rb * rows, hipMemcpyHostToDevice, e->stream));
+        else HL_HIP_CHECK(hipMemcpy2DAsync(e->d_stage + at[c], rb, f.plane[c], pitch, rb, rows, hipMemcpyHostToDevice, e->stream));
+        S->plane[c] = e->d_stage + at[c];
+        S->pitch[c] = (int64_t)rb;
+    }
+    return HL_AMD_SUCCESS;
+}
+
+// one (checked, not forwarded) frame into the planes dst: the call's one launch
+static int32_t in_one(hl_amd_encoder_t* e, const hl_amd_frame_t& f, uint8_t* const* dst)
+{
+    InArgs A{};
+    if (f.on_device) A.one = in_describe(e, f);
+    else {
+        const int32_t rc = in_stage(e, f, &A.one);
+        if (rc) return rc;
+    }
+    for (int c = 0; c < 3; ++c) A.one.dst[c] = dst[c];
+    A.coef = in_coef_of(e->in_matrix, e->in_range);
+    A.W = e->W;
+    A.H = e->H;
+    HL_HIP_CHECK(launch_ingest(A, f.format, 1, e->stream));
+    e->in_launches.push_back({A, f.format, 1});
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_set_colour(hl_amd_encoder_t* e, int32_t matrix, int32_t range)
+{
+    if (!e || matrix < HL_AMD_MATRIX_BT601 || matrix > HL_AMD_MATRIX_BT709 || range < HL_AMD_RANGE_LIMITED || range > HL_AMD_RANGE_FULL)
+        return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;  // queued frames come first (hl_amd_flush)
+    e->in_matrix = matrix;
+    e->in_range = range;
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_encode_frame(hl_amd_encoder_t* e, const hl_amd_frame_t* f, const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* r)
+{
+    if (!e || !f || !r) return HL_AMD_ERROR_INVALID_PARAMETER;
+    e->in_ok = false;
+    if (e->lookahead <= 1) quality_drop(e);  // a refused or failed call leaves no results (with look-ahead: as hl_amd_encode_ex, when the queue is coded)
+    if (e->svc) return HL_AMD_ERROR_NOT_IMPLEMENTED;
+    int32_t rc = check_frames(e, f, 1, false);
+    if (rc == HL_AMD_SUCCESS) rc = check_ctl(e, ctl, 1);
+    if (rc) return rc;
+    if (e->broken) return HL_AMD_ERROR_INVALID_STATE;  // before anything is uploaded or launched
+    const bool fwd = in_forwarded(e, *f);
+    const size_t ny = (size_t)e->W * e->H, nc = (size_t)e->Wc * e->Hc, fb = ny + 2 * nc;
+    e->in_launches.clear();
+    e->in_src.assign(3, nullptr);
+    if (e->lookahead > 1) {  // as hl_amd_encode_ex: the frame goes into the queue's next slot, a full queue is coded
+        if (!e->d_la) HL_HIP_CHECK(hipMalloc(&e->d_la, fb * e->lookahead));
+        uint8_t* d = e->d_la + fb * e->la_n;
+        uint8_t* const dst[3] = {d, d + ny, d + ny + nc};
+        if (fwd) {
+            for (int c = 0; c < 3; ++c) HL_HIP_CHECK(hipMemcpyAsync(dst[c], f->plane[c], c ? nc : ny, hipMemcpyDeviceToDevice, e->stream));
+        }
+        else {
+            rc = in_one(e, *f, dst);
+            if (rc) return rc;
+        }
+        HL_HIP_CHECK(hipStreamSynchronize(e->stream));  // the caller may reuse its buffer
+        e->la_ctl.resize(e->lookahead);
+        e->la_has_ctl.resize(e->lookahead);
+        e->la_has_ctl[e->la_n] = ctl != nullptr;
+        if (ctl) e->la_ctl[e->la_n] = *ctl;
+        if (++e->la_n == e->lookahead) {
+            e->in_nested = true;
+            rc = la_run(e);
+            e->in_nested = false;
+            if (rc) return rc;
+        }
+        la_pop(e, r);
+        e->in_ok = true;
+        return HL_AMD_SUCCESS;
+    }
+    const uint8_t* src[3] = {f->plane[0], f->plane[1], f->plane[2]};
+    if (!fwd) {
+        rc = in_one(e, *f, e->d_in);
+        if (rc) return rc;
+        for (int c = 0; c < 3; ++c) src[c] = e->in_src[c] = e->d_in[c];
+    }
+    e->in_nested = true;
+    rc = encode_pictures(e, 1, &src[0], &src[1], &src[2], r, ctl);
+    e->in_nested = false;
+    e->in_ok = rc == HL_AMD_SUCCESS;
+    return rc;
+}
+
+extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl_amd_frame_t* f, const hl_amd_frame_ctl_t* ctl,
+                                        hl_amd_result_t* results)
+{
+    if (!e || n <= 0 || !f || !results) return HL_AMD_ERROR_INVALID_PARAMETER;
+    e->in_ok = false;
+    quality_drop(e);  // a refused or failed call leaves no results
+    if (e->svc) return HL_AMD_ERROR_NOT_IMPLEMENTED;
+    int32_t rc = check_frames(e, f, n, true);
+    if (rc) return rc;
+    if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;  // frames still queued by the look-ahead come first (hl_amd_flush)
+    rc = check_ctl(e, ctl, n);
+    if (rc) return rc;
+    if (e->broken) return HL_AMD_ERROR_INVALID_STATE;  // before anything is converted
+    const size_t ny = (size_t)e->W * e->H, nc = (size_t)e->Wc * e->Hc, fb = ny + 2 * nc;
+    size_t m = 0;  // frames to convert
+    for (int i = 0; i < n; ++i) m += !in_forwarded(e, f[i]);
+    if (e->inb_cap < fb * m) {
+        (void)hipFree(e->d_inb);
+        e->d_inb = nullptr;
+        e->inb_cap = 0;
+        if (hipMalloc(&e->d_inb, fb * m) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e->inb_cap = fb * m;
+    }
+    if (e->in_tab_cap < m) {
+        (void)hipFree(e->d_in_tab);
+        e->d_in_tab = nullptr;
+        e->in_tab_cap = 0;
+        if (hipMalloc(&e->d_in_tab, sizeof(InFrame) * m) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e->in_tab_cap = m;
+    }
+    // the table, format by format (one launch per format); frame i keeps its place in the call
+    e->in_launches.clear();
+    e->in_src.assign((size_t)3 * n, nullptr);
+    e->in_tab.clear();
+    std::vector<const uint8_t*> y(n), u(n), v(n);
+    size_t first[IN_FORMATS + 1] = {};
+    for (int fmt = 0; fmt < IN_FORMATS; ++fmt) {
+        first[fmt] = e->in_tab.size();
+        for (int i = 0; i < n; ++i) {
+            if (f[i].format != fmt || in_forwarded(e, f[i])) continue;
+            InFrame F = in_describe(e, f[i]);
+            uint8_t* d = e->d_inb + fb * e->in_tab.size();
+            y[i] = e->in_src[3 * (size_t)i] = F.dst[0] = d;
+            u[i] = e->in_src[3 * (size_t)i + 1] = F.dst[1] = d + ny;
+            v[i] = e->in_src[3 * (size_t)i + 2] = F.dst[2] = d + ny + nc;
+            e->in_tab.push_back(F);
+        }
+    }
+    first[IN_FORMATS] = e->in_tab.size();
+    for (int i = 0; i < n; ++i)
+        if (in_forwarded(e, f[i])) {
+            y[i] = f[i].plane[0];
+            u[i] = f[i].plane[1];
+            v[i] = f[i].plane[2];
+        }
+    if (m) HL_HIP_CHECK(hipMemcpyAsync(e->d_in_tab, e->in_tab.data(), sizeof(InFrame) * m, hipMemcpyHostToDevice, e->stream));
+    for (int fmt = 0; fmt < IN_FORMATS; ++fmt)
+        for (size_t f0 = first[fmt]; f0 < first[fmt + 1]; f0 += 65535) {  // grid z holds the frames
+            InArgs A{};
+            A.tab = e->d_in_tab + f0;
+            A.coef = in_coef_of(e->in_matrix, e->in_range);
+            A.W = e->W;
+            A.H = e->H;
+            const int frames = (int)std::min<size_t>(65535, first[fmt + 1] - f0);
+            HL_HIP_CHECK(launch_ingest(A, fmt, frames, e->stream));
+            e->in_launches.push_back({A, fmt, frames});
+        }
+    e->in_nested = true;
+    rc = encode_pictures(e, n, y.data(), u.data(), v.data(), results, ctl);
+    e->in_nested = false;
+    e->in_ok = rc == HL_AMD_SUCCESS;
+    return rc;
+}
+
+extern "C" int32_t hl_amd_get_input(hl_amd_encoder_t* e, int32_t k, uint8_t* y, uint8_t* u, uint8_t* v)
+{
+    if (!e || !y || !u || !v || k < 0) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->in_ok || e->lookahead > 1) return HL_AMD_ERROR_INVALID_STATE;
+    if ((size_t)3 * k + 2 >= e->in_src.size()) return HL_AMD_ERROR_INVALID_PARAMETER;
+    const uint8_t* const* p = &e->in_src[(size_t)3 * k];
+    if (!p[0]) return HL_AMD_ERROR_INVALID_STATE;  // forwarded: the planes are the caller's
+    HL_HIP_CHECK(hipMemcpyAsync(y, p[0], (size_t)e->W * e->H, hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipMemcpyAsync(u, p[1], (size_t)e->Wc * e->Hc, hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipMemcpyAsync(v, p[2], (size_t)e->Wc * e->Hc, hipMemcpyDeviceToHost, e->stream));
+    HL_HIP_CHECK(hipStreamSynchronize(e->stream));
+    return HL_AMD_SUCCESS;
+}
+
+// k_ingest alone: `iters` times the launches of the last frame call (the same
+// frames into the same planes), timed with HIP events on the encoder's stream;
+// *ms = average milliseconds per repetition.  Diagnostics, like hl_amd_bench_planes.
+extern "C" int32_t hl_amd_bench_ingest(hl_amd_encoder_t* e, int32_t iters, float* ms)
+{
+    if (!e || iters <= 0 || !ms) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->in_ok || e->in_launches.empty()) return HL_AMD_ERROR_INVALID_STATE;
+    hipEvent_t a, b;
+    HL_HIP_CHECK(hipEventCreate(&a));
+    HL_HIP_CHECK(hipEventCreate(&b));
+    for (const auto& L : e->in_launches) HL_HIP_CHECK(launch_ingest(L.A, L.fmt, L.frames, e->stream));  // warm
+    HL_HIP_CHECK(hipEventRecord(a, e->stream));
+    for (int i = 0; i < iters; ++i)
+        for (const auto& L : e->in_launches) HL_HIP_CHECK(launch_ingest(L.A, L.fmt, L.frames, e->stream));
+    HL_HIP_CHECK(hipEventRecord(b, e->stream));
+    HL_HIP_CHECK(hipEventSynchronize(b));
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, a, b);
+    *ms = t / iters;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return HL_AMD_SUCCESS;
 }
 
 extern "C" int32_t hl_amd_get_recon(hl_amd_encoder_t* e, uint8_t* y, uint8_t* u, uint8_t* v)

@@ -564,6 +564,106 @@ int32_t hl_amd_bench_quality(hl_amd_encoder_t* encoder, int32_t iters, float* ms
 double hl_amd_psnr_db(uint64_t sse, uint64_t samples);
 double hl_amd_ssim_mean(int64_t q30, uint64_t windows);
 
+/* ---- frames that are not dense planar I420 ----
+ * No reference interface: hl_frame_video_t (hl_frame.h:278-291) has neither a
+ * pitch nor a format.  A frame is described by its format, its planes and the
+ * bytes between their rows; the picture size is the encoder's.  Row bytes per
+ * plane: I420 W, W/2, W/2; NV12 W, W; RGB24 3W; RGBA32 4W (byte 3 of a sample
+ * is ignored); RGBP W, W, W.  Only the bytes [plane + r pitch, plane + r pitch
+ * + row bytes) of a row are ever read: a plane's last row needs no padding
+ * after it (a cropped view of a larger image works).
+ * One GPU kernel (k_ingest, hartallo_amd/csrc/hl_ingest.h) turns the frame
+ * into the dense I420 planes the unchanged coding path takes:
+ *   - I420 and NV12 are copied (de-pitched, NV12's chroma de-interleaved);
+ *   - RGB is converted with integers only,
+ *       Y = (yr R + yg G + yb B + (off << 16) + (1 << 15)) >> 16 per sample,
+ *       U = min(255, (ur SR + ug SG + ub SB + (128 << 18) + (1 << 17)) >> 18)
+ *     and V likewise per 2x2 block from the sums SR, SG, SB of its four
+ *     samples (chroma sited at the block's centre, rounded once).  Tables
+ *     (y | u | v | off), derived in hl_ingest.h from Kr, Kb and the range:
+ *       601 limited (16829 33039 6416 | -9714 -19070 28784 | 28784 -24103 -4681 | 16)
+ *       601 full    (19595 38470 7471 | -11058 -21710 32768 | 32768 -27439 -5329 | 0)
+ *       709 limited (11966 40254 4064 | -6596 -22188 28784 | 28784 -26145 -2639 | 16)
+ *       709 full    (13933 46871 4732 | -7509 -25259 32768 | 32768 -29763 -3005 | 0)
+ *     Grey input gives U = V = 128 exactly.  The default is BT.601 limited.
+ *     The stream carries no VUI colour description (the reference writes
+ *     none): which matrix was used travels out of band.
+ * Picture sizes stay multiples of 16; spatial layers are not served
+ * (HL_AMD_ERROR_NOT_IMPLEMENTED). */
+enum {
+    HL_AMD_FORMAT_I420 = 0,
+    HL_AMD_FORMAT_NV12,
+    HL_AMD_FORMAT_RGB24,
+    HL_AMD_FORMAT_RGBA32,
+    HL_AMD_FORMAT_RGBP
+};
+enum { HL_AMD_MATRIX_BT601 = 0, HL_AMD_MATRIX_BT709 };
+enum { HL_AMD_RANGE_LIMITED = 0, HL_AMD_RANGE_FULL };
+
+typedef struct hl_amd_frame_s {
+    int32_t format, on_device; /* HL_AMD_FORMAT_*; on_device: planes in HBM, else host */
+    const uint8_t* plane[3];   /* I420: Y,U,V  NV12: Y,UV  RGB24/RGBA32: one  RGBP: R,G,B */
+    int64_t pitch[3];          /* bytes between rows; 0 = dense (row bytes) */
+} hl_amd_frame_t;
+
+/* Validation of the frame calls below covers every frame of a call and
+ * happens before anything is uploaded, converted or queued; a refused call
+ * leaves the encoder as it was and the next call continues the stream.
+ * HL_AMD_ERROR_INVALID_PARAMETER: an unknown format; a null plane the format
+ * needs; a pitch that is negative, or non-zero and below row bytes; a device
+ * plane or pitch that is no multiple of 4 (k_ingest loads 4-byte words).
+ * HL_AMD_ERROR_NOT_IMPLEMENTED: an encoder with spatial layers.  The ctl is
+ * checked as in the _ex calls.  HL_AMD_ERROR_INVALID_STATE: an encoder that
+ * an earlier GPU failure has left unusable.
+ * A dense I420 frame in device memory (every pitch 0 or row bytes) is
+ * forwarded untouched -- no copy, no kernel: it is hl_amd_encode_device_ex's
+ * frame, the 4-byte rule does not apply to it, and the alignment rules of
+ * scene-cut detection and quality apply to the caller's planes as there.
+ * (With look-ahead on, hl_amd_encode_frame copies such a frame into the queue
+ * as hl_amd_encode_ex does, and no alignment rule applies to it.) */
+
+/* The matrix and range RGB frames are converted with from now on
+ * (HL_AMD_MATRIX_*, HL_AMD_RANGE_*; anything else
+ * HL_AMD_ERROR_INVALID_PARAMETER).  Between any two encode calls; while
+ * look-ahead frames are queued HL_AMD_ERROR_INVALID_STATE.  No reference
+ * interface (see above). */
+int32_t hl_amd_set_colour(hl_amd_encoder_t* encoder, int32_t matrix, int32_t range);
+
+/* One frame: hl_amd_encode_ex / hl_amd_encode_device_ex for a described
+ * frame.  A host frame is uploaded row by row (padding is not read) into a
+ * staging buffer the encoder owns, a device frame is read in place; one
+ * k_ingest launch on the encoder's stream writes the encoder's input planes
+ * (with look-ahead: the queue's next slot), and the frame then goes through
+ * exactly what those calls run: the result, the GOP counter, rate control,
+ * scene cuts and quality (source = the converted planes) are theirs.  No
+ * reference interface (see above). */
+int32_t hl_amd_encode_frame(hl_amd_encoder_t* encoder, const hl_amd_frame_t* frame, const hl_amd_frame_ctl_t* ctl,
+                            hl_amd_result_t* result);
+
+/* n frames in device memory (a host frame: HL_AMD_ERROR_INVALID_PARAMETER):
+ * hl_amd_encode_batch_ex for described frames.  Every frame that is not
+ * forwarded is converted first, into a buffer of dense I420 frames the encoder
+ * owns -- one k_ingest launch per format the call holds -- and the n frames
+ * are then coded as by hl_amd_encode_batch_ex: its results, its split into
+ * runs and its failure contract.  HL_AMD_ERROR_INVALID_STATE while look-ahead
+ * frames are queued.  No reference interface (see above). */
+int32_t hl_amd_encode_frames(hl_amd_encoder_t* encoder, int32_t n, const hl_amd_frame_t* frames, const hl_amd_frame_ctl_t* ctl,
+                             hl_amd_result_t* results);
+
+/* The planes picture k of the last hl_amd_encode_frame / hl_amd_encode_frames
+ * call was coded from, copied to the host: what was encoded.
+ * HL_AMD_ERROR_INVALID_STATE before such a call, after a refused or failed
+ * one, after any other encode call, for a forwarded frame (its planes are the
+ * caller's) and with look-ahead on.  No reference interface (see above). */
+int32_t hl_amd_get_input(hl_amd_encoder_t* encoder, int32_t k, uint8_t* y, uint8_t* u, uint8_t* v);
+
+/* Diagnostics: `iters` times the k_ingest launch(es) of the last frame call
+ * (the same frames, which must still be there, into the same planes); *ms =
+ * average ms per repetition.  HL_AMD_ERROR_INVALID_STATE when that call
+ * launched nothing (every frame forwarded) or did not succeed.  No reference
+ * interface (like hl_amd_bench_pyramid). */
+int32_t hl_amd_bench_ingest(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
+
 /* device time (ms) of the enhancement layers of the last access unit (with
  * hl_amd_set_timing on) */
 float hl_amd_svc_layer_ms(hl_amd_encoder_t* encoder);
