@@ -60,6 +60,9 @@ EXPORTED_SYMBOLS = (
     "hl_amd_set_pipeline",
     "hl_amd_set_rate_control",
     "hl_amd_set_max_ref_frame",
+    "hl_amd_set_display_size",
+    "hl_amd_get_display_size",
+    "hl_amd_stream_headers",
     "hl_amd_last_qp",
     "hl_amd_pipeline_occupancy",
     "hl_amd_set_pipeline_build",
@@ -351,6 +354,22 @@ def ssim_mean(q30: int, windows: int) -> float:
     return load_library().hl_amd_ssim_mean(q30, windows)
 
 
+def stream_headers(width: int, height: int, qp: int = 28, max_ref_frame: int = 1, display_width: "int | None" = None,
+                   display_height: "int | None" = None) -> bytes:
+    """The SPS and PPS (with start codes) of an encoder of the coded size width
+    x height after set_max_ref_frame(max_ref_frame) and set_display_size(
+    display_width, display_height) -- None: the coded size, no cropping
+    (hl_amd_stream_headers; no device).  ValueError for settings an encoder
+    refuses."""
+    p = _Params(width, height, qp, 16, 1, 30, 0, 0)
+    buf = ctypes.create_string_buffer(256)
+    n = load_library().hl_amd_stream_headers(ctypes.byref(p), max_ref_frame, width if display_width is None else display_width,
+                                             height if display_height is None else display_height, buf, len(buf))
+    if not n:
+        raise ValueError("stream_headers: a size or setting the encoder refuses")
+    return buf.raw[:n]
+
+
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     """Loads the HIP library.  torch (if installed) is imported first so the
     process ends up with one HIP runtime (torch ships its own
@@ -396,6 +415,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "hl_amd_set_max_ref_frame"):  # (absent from builds before round 5 loaded through HL_LIB)
         lib.hl_amd_set_max_ref_frame.argtypes = [vp, i32]
         lib.hl_amd_set_max_ref_frame.restype = i32
+    if hasattr(lib, "hl_amd_set_display_size"):  # (absent from builds before the display size loaded through HL_LIB)
+        lib.hl_amd_set_display_size.argtypes = [vp, i32, i32]
+        lib.hl_amd_set_display_size.restype = i32
+        lib.hl_amd_get_display_size.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        lib.hl_amd_get_display_size.restype = i32
+        lib.hl_amd_stream_headers.argtypes = [ctypes.POINTER(_Params), i32, i32, i32, vp, ctypes.c_size_t]
+        lib.hl_amd_stream_headers.restype = ctypes.c_size_t
     lib.hl_amd_last_qp.argtypes = [vp]
     lib.hl_amd_last_qp.restype = i32
     lib.hl_amd_pipeline_occupancy.argtypes = []
@@ -658,6 +684,28 @@ class Encoder:
         if rc:
             raise HlAmdError(rc, "hl_amd_set_max_ref_frame")
 
+    def set_display_size(self, width: int, height: int) -> None:
+        """The size a decoder shows (hl_amd_set_display_size): even, within the
+        last macroblock column and row of the coded size the encoder was
+        created with.  The SPS then carries the cropping offsets, encode_frame
+        and encode_frames_device take frames of this size and pad them on the
+        GPU by edge replication, and quality covers the display rectangle;
+        encode, encode_device and encode_batch_device keep taking planes of the
+        coded size.  Before the first frame."""
+        rc = self.lib.hl_amd_set_display_size(self._h, width, height)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_set_display_size")
+        w, h = ctypes.c_int32(), ctypes.c_int32()
+        rc = self.lib.hl_amd_get_display_size(self._h, ctypes.byref(w), ctypes.byref(h))
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_get_display_size")
+        self._display = (w.value, h.value)
+
+    @property
+    def display_size(self):
+        """(width, height) a decoder shows: the coded size unless set_display_size set another."""
+        return getattr(self, "_display", None) or (self.width, self.height)
+
     def last_qp(self) -> int:
         """SliceQPY of the last encoded picture."""
         return self.lib.hl_amd_last_qp(self._h)
@@ -754,7 +802,8 @@ class Encoder:
             raise HlAmdError(rc, "hl_amd_set_colour")
 
     def _check_frame(self, f: "Frame"):
-        if f.width and (f.width, f.height) != (self.width, self.height):
+        """a frame of a known size has the display size (the coded size unless one was set)"""
+        if f.width and (f.width, f.height) != self.display_size:
             raise HlAmdError(HL_AMD_ERROR_INVALID_FORMAT, "frame (picture size)")
 
     def encode_frame(self, frame: "Frame", ctl: "FrameCtl | None" = None) -> EncodeResult:

@@ -1149,6 +1149,9 @@ struct hl_amd_encoder_s {
     std::vector<std::vector<uint8_t>> bout;  // bitstreams of the last hl_amd_encode_batch
     int nwriters;                            // host slice writer threads of a run
     int32_t max_ref_frame = 1;               // hl_codec_t.max_ref_frame: SPS/PPS fields only (hl_amd_set_max_ref_frame)
+    // hl_amd_set_display_size (W x H from create on: none): the SPS's cropping
+    // fields, the size of the frame calls' frames and the quality window
+    int32_t dW = 0, dH = 0;
     std::vector<std::vector<uint8_t>> wscratch, wout;
     std::vector<PicPlan> run_plan;               // per picture of the run: its type (IDR or P) and settings (plan_picture)
     std::vector<int32_t> run_idr_id;             // per picture of the run: idr_pic_id
@@ -1225,7 +1228,7 @@ struct hl_amd_encoder_s {
     // encoder's stream into d_in, a look-ahead slot or d_inb before the call
     // is coded from those planes
     int32_t in_matrix = 0, in_range = 0;         // hl_amd_set_colour
-    uint8_t* d_stage = nullptr;                  // a host frame's rows, plane by plane, dense (256-byte aligned planes)
+    uint8_t* d_stage = nullptr;                  // a host frame's rows, plane by plane, pitch = row bytes rounded up to 4 (256-byte aligned planes)
     size_t stage_cap = 0;
     uint8_t* d_inb = nullptr;                    // hl_amd_encode_frames: the converted frames, Y | U | V each
     size_t inb_cap = 0;
@@ -1320,6 +1323,8 @@ extern "C" int32_t hl_amd_encoder_create(const hl_amd_params_t* p, hl_amd_encode
     e->H = p->height;
     e->Wc = e->W / 2;
     e->Hc = e->H / 2;
+    e->dW = e->W;
+    e->dH = e->H;
     e->mbw = e->W / 16;
     e->mbh = e->H / 16;
     e->nmb = e->mbw * e->mbh;
@@ -1653,6 +1658,10 @@ static hipError_t quality_launch_tab(hl_amd_encoder_t* e, int m, int slot)
     A.mb = e->d_q_mb[0] + (size_t)e->nmb * slot;
     A.W = e->W;
     A.H = e->H;
+    if (e->dW != e->W || e->dH != e->H) {  // hl_amd_set_display_size: the display rectangle only
+        A.dW = e->dW;
+        A.dH = e->dH;
+    }
     return hl::launch_quality(A, m, e->stream);
 }
 
@@ -2579,6 +2588,14 @@ extern "C" int32_t hl_amd_encode_batch_ex(hl_amd_encoder_t* e, int32_t n, const 
     return encode_pictures(e, n, y, u, v, results, ctl);
 }
 
+// e->hdr from every setting the SPS and PPS carry (max_ref_frame, the display size)
+static void rebuild_headers(hl_amd_encoder_t* e)
+{
+    const StreamParams sp{e->W, e->H, e->p.qp, e->p.deblock, e->max_ref_frame, e->dW, e->dH};
+    e->hdr.resize(256);
+    e->hdr.resize(write_stream_headers(sp, e->hdr.data(), e->hdr.size()));
+}
+
 extern "C" int32_t hl_amd_set_max_ref_frame(hl_amd_encoder_t* e, int32_t max_ref_frame)
 {
     // any value: the SPS carries min(MaxDpbMbs / PicSizeInMbs, max_ref_frame)
@@ -2588,10 +2605,49 @@ extern "C" int32_t hl_amd_set_max_ref_frame(hl_amd_encoder_t* e, int32_t max_ref
     // the reference reads it once, when it builds the first SPS (sps.c:620-636)
     if (e->frame_index != 0 || svc_started(e)) return HL_AMD_ERROR_INVALID_STATE;
     e->max_ref_frame = max_ref_frame;
-    const StreamParams sp{e->W, e->H, e->p.qp, e->p.deblock, e->max_ref_frame};
-    e->hdr.resize(256);
-    e->hdr.resize(write_stream_headers(sp, e->hdr.data(), e->hdr.size()));
+    rebuild_headers(e);
     return HL_AMD_SUCCESS;
+}
+
+static bool display_set(const hl_amd_encoder_t* e) { return e->dW != e->W || e->dH != e->H; }
+
+// The display size (no reference interface: the reference refuses pictures
+// that are no multiples of 16, hl_codec_264.c:430-433, and always writes
+// frame_cropping_flag = 0, hl_codec_264_sps.c:625).  Like max_ref_frame it is
+// part of the SPS, so it is taken only before the first picture.
+extern "C" int32_t hl_amd_set_display_size(hl_amd_encoder_t* e, int32_t width, int32_t height)
+{
+    if (!e) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->svc) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // (the subset SPS is not touched)
+    if (!display_size_ok(e->W, e->H, width, height)) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->frame_index != 0 || e->la_n) return HL_AMD_ERROR_INVALID_STATE;
+    e->dW = width;
+    e->dH = height;
+    rebuild_headers(e);
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_get_display_size(hl_amd_encoder_t* e, int32_t* width, int32_t* height)
+{
+    if (!e || !width || !height) return HL_AMD_ERROR_INVALID_PARAMETER;
+    *width = e->dW;
+    *height = e->dH;
+    return HL_AMD_SUCCESS;
+}
+
+// the SPS and PPS of an encoder with these settings (a pure function; no device)
+extern "C" size_t hl_amd_stream_headers(const hl_amd_params_t* p, int32_t max_ref_frame, int32_t display_width, int32_t display_height,
+                                        uint8_t* out, size_t cap)
+{
+    if (!p || !out || p->width <= 0 || p->height <= 0 || (p->width & 15) || (p->height & 15) || p->qp < 0 || p->qp > 51) return 0;
+    if (max_ref_frame < 0 || sps_max_num_ref_frames(p->width, p->height, max_ref_frame) > 16) return 0;
+    if (!display_size_ok(p->width, p->height, display_width, display_height)) return 0;
+    const StreamParams sp{p->width, p->height, p->qp, p->deblock, max_ref_frame, display_width, display_height};
+    uint8_t buf[256];
+    const size_t n = write_stream_headers(sp, buf, sizeof(buf));
+    if (n > cap) return 0;
+    memcpy(out, buf, n);
+    return n;
 }
 
 extern "C" int32_t hl_amd_set_rate_control(hl_amd_encoder_t* e, int64_t bitrate, int32_t fps_num, int32_t fps_den,
@@ -2828,13 +2884,17 @@ extern "C" int32_t hl_amd_last_quality(hl_amd_encoder_t* e, int32_t layer, int32
     if (!quality_have(e, layer, k)) return HL_AMD_ERROR_INVALID_STATE;
     int W, H;
     svc_layer_size(e, layer, W, H);
+    if (!e->svc) {  // the display rectangle (the picture itself without a display size)
+        W = e->dW;
+        H = e->dH;
+    }
     const unsigned long long* s = e->h_q_sums + (size_t)6 * ((size_t)layer * e->q_cap + k);
     for (int c = 0; c < 3; ++c) {
-        const uint64_t w = c ? W >> 1 : W, h = c ? H >> 1 : H;
+        const int w = c ? W >> 1 : W, h = c ? H >> 1 : H;
         out->sse[c] = s[2 * c];
-        out->samples[c] = w * h;
+        out->samples[c] = (uint64_t)w * (uint64_t)h;
         out->ssim_q30[c] = (int64_t)s[2 * c + 1];
-        out->windows[c] = (w / 4 - 1) * (h / 4 - 1);
+        out->windows[c] = hl::q_windows(w, h);
     }
     return HL_AMD_SUCCESS;
 }
@@ -2946,12 +3006,15 @@ extern "C" int32_t hl_amd_encode_ex(hl_amd_encoder_t* e, const uint8_t* y, const
 // interface: hl_frame_video_t has neither a pitch nor a format).  k_ingest
 // (hl_ingest.h) writes dense I420 planes on the encoder's stream -- one launch
 // per call and format -- and the call is then coded from those planes by
-// encode_pictures or the look-ahead queue: every rule is theirs.
+// encode_pictures or the look-ahead queue: every rule is theirs.  With a
+// display size below the coded size (hl_amd_set_display_size) the frames have
+// that size, and launch_ingest's second kernel, k_ingest_edge, pads the planes
+// to the coded size by edge replication; everything after it sees W x H planes.
 // ---------------------------------------------------------------------------
 // a dense I420 frame in device memory: coded from the caller's planes as it is
 static bool in_forwarded(const hl_amd_encoder_t* e, const hl_amd_frame_t& f)
 {
-    if (!f.on_device || f.format != HL_AMD_FORMAT_I420) return false;
+    if (!f.on_device || f.format != HL_AMD_FORMAT_I420 || display_set(e)) return false;  // (a frame below the coded size is padded by k_ingest_edge)
     for (int c = 0; c < 3; ++c)
         if (f.pitch[c] && f.pitch[c] != in_row_bytes(IN_I420, c, e->W)) return false;
     return true;
@@ -2964,16 +3027,18 @@ static int32_t check_frames(const hl_amd_encoder_t* e, const hl_amd_frame_t* f, 
     for (int i = 0; i < n; ++i) {
         if (f[i].format < 0 || f[i].format >= IN_FORMATS) return HL_AMD_ERROR_INVALID_PARAMETER;
         if (device_only && !f[i].on_device) return HL_AMD_ERROR_INVALID_PARAMETER;
-        for (int c = 0; c < in_planes(f[i].format); ++c)
-            if (!f[i].plane[c] || f[i].pitch[c] < 0 || (f[i].pitch[c] && f[i].pitch[c] < in_row_bytes(f[i].format, c, e->W)))
+        for (int c = 0; c < in_planes(f[i].format); ++c)  // (a frame has the display size: the coded size unless one was set)
+            if (!f[i].plane[c] || f[i].pitch[c] < 0 || (f[i].pitch[c] && f[i].pitch[c] < in_row_bytes(f[i].format, c, e->dW)))
                 return HL_AMD_ERROR_INVALID_PARAMETER;
         if (in_forwarded(e, f[i])) {  // the caller's planes are what scene-cut detection and quality read, unless the frame is queued
             if (!queued && (!quality_aligned(e, f[i].plane[0], f[i].plane[1], f[i].plane[2]) || (e->sc_thr && ((uintptr_t)f[i].plane[0] & 3))))
                 return HL_AMD_ERROR_INVALID_PARAMETER;
         }
-        else if (f[i].on_device) {  // k_ingest loads 4-byte words
-            for (int c = 0; c < in_planes(f[i].format); ++c)
-                if (((uintptr_t)f[i].plane[c] | (uint64_t)f[i].pitch[c]) & 3) return HL_AMD_ERROR_INVALID_PARAMETER;
+        else if (f[i].on_device) {  // k_ingest loads 4-byte words (a dense row of a display width like 34 is no multiple of 4)
+            for (int c = 0; c < in_planes(f[i].format); ++c) {
+                const uint64_t pitch = f[i].pitch[c] ? (uint64_t)f[i].pitch[c] : (uint64_t)in_row_bytes(f[i].format, c, e->dW);
+                if (((uintptr_t)f[i].plane[c] | pitch) & 3) return HL_AMD_ERROR_INVALID_PARAMETER;
+            }
         }
     }
     return HL_AMD_SUCCESS;
@@ -2985,18 +3050,21 @@ static InFrame in_describe(const hl_amd_encoder_t* e, const hl_amd_frame_t& f)
     InFrame F{};
     for (int c = 0; c < in_planes(f.format); ++c) {
         F.plane[c] = f.plane[c];
-        F.pitch[c] = f.pitch[c] ? f.pitch[c] : in_row_bytes(f.format, c, e->W);
+        F.pitch[c] = f.pitch[c] ? f.pitch[c] : in_row_bytes(f.format, c, e->dW);
     }
     return F;
 }
 
-// a (checked) host frame's rows into d_stage, plane by plane and dense: padding is not read
+// a (checked) host frame's rows into d_stage, plane by plane, with the row
+// bytes rounded up to a multiple of 4 as the pitch (k_ingest's word loads; the
+// coded size's rows are such multiples, a display width like 34 is not):
+// padding is not read
 static int32_t in_stage(hl_amd_encoder_t* e, const hl_amd_frame_t& f, InFrame* S)
 {
     size_t at[3] = {}, total = 0;
     for (int c = 0; c < in_planes(f.format); ++c) {
         at[c] = total;
-        total += ((size_t)in_row_bytes(f.format, c, e->W) * in_rows(f.format, c, e->H) + 255) & ~(size_t)255;
+        total += ((((size_t)in_row_bytes(f.format, c, e->dW) + 3) & ~(size_t)3) * in_rows(f.format, c, e->dH) + 255) & ~(size_t)255;
     }
     if (e->stage_cap < total) {
         (void)hipFree(e->d_stage);
@@ -3006,12 +3074,12 @@ static int32_t in_stage(hl_amd_encoder_t* e, const hl_amd_frame_t& f, InFrame* S
         e->stage_cap = total;
     }
     for (int c = 0; c < in_planes(f.format); ++c) {
-        const size_t rb = (size_t)in_row_bytes(f.format, c, e->W), rows = (size_t)in_rows(f.format, c, e->H);
+        const size_t rb = (size_t)in_row_bytes(f.format, c, e->dW), rows = (size_t)in_rows(f.format, c, e->dH), sp = (rb + 3) & ~(size_t)3;
         const size_t pitch = f.pitch[c] ? (size_t)f.pitch[c] : rb;
-        if (pitch == rb) HL_HIP_CHECK(hipMemcpyAsync(e->d_stage + at[c], f.plane[c], rb * rows, hipMemcpyHostToDevice, e->stream));
-        else HL_HIP_CHECK(hipMemcpy2DAsync(e->d_stage + at[c], rb, f.plane[c], pitch, rb, rows, hipMemcpyHostToDevice, e->stream));
+        if (pitch == rb && sp == rb) HL_HIP_CHECK(hipMemcpyAsync(e->d_stage + at[c], f.plane[c], rb * rows, hipMemcpyHostToDevice, e->stream));
+        else HL_HIP_CHECK(hipMemcpy2DAsync(e->d_stage + at[c], sp, f.plane[c], pitch, rb, rows, hipMemcpyHostToDevice, e->stream));
         S->plane[c] = e->d_stage + at[c];
-        S->pitch[c] = (int64_t)rb;
+        S->pitch[c] = (int64_t)sp;
     }
     return HL_AMD_SUCCESS;
 }
@@ -3029,6 +3097,8 @@ static int32_t in_one(hl_amd_encoder_t* e, const hl_amd_frame_t& f, uint8_t* con
     A.coef = in_coef_of(e->in_matrix, e->in_range);
     A.W = e->W;
     A.H = e->H;
+    A.dW = e->dW;
+    A.dH = e->dH;
     HL_HIP_CHECK(launch_ingest(A, f.format, 1, e->stream));
     e->in_launches.push_back({A, f.format, 1});
     return HL_AMD_SUCCESS;
@@ -3160,6 +3230,8 @@ extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl
             A.coef = in_coef_of(e->in_matrix, e->in_range);
             A.W = e->W;
             A.H = e->H;
+            A.dW = e->dW;
+            A.dH = e->dH;
             const int frames = (int)std::min<size_t>(65535, first[fmt + 1] - f0);
             HL_HIP_CHECK(launch_ingest(A, fmt, frames, e->stream));
             e->in_launches.push_back({A, fmt, frames});
@@ -3735,6 +3807,7 @@ extern "C" int32_t hl_amd_add_layer(hl_amd_encoder_t* e, int32_t width, int32_t 
 {
     if (!e || width <= 0 || height <= 0) return HL_AMD_ERROR_INVALID_PARAMETER;
     if (e->frame_index > 0 || e->la_n || (e->svc && e->svc->started)) return HL_AMD_ERROR_INVALID_STATE;
+    if (display_set(e)) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // hl_amd_set_display_size is AVC only (the subset SPS carries no cropping)
     e->lookahead = 1;  // (the look-ahead is AVC only: an encoder with layers ignores it)
     e->sc_thr = 0;     // (scene-cut detection too: layers take no forced types)
     e->sc_have_prev = false;

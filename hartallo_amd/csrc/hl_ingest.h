@@ -29,7 +29,8 @@
 // cross-lane traffic, no atomics.  A workgroup is 64 x 4 lanes: a wave owns 64
 // consecutive tiles of one row pair (its loads of a sample row are one
 // contiguous run, 1 KiB of luma), the four waves four row pairs.  W and H are
-// multiples of 16: there are no partial tiles, only lanes beyond the picture.
+// multiples of 16: there are no partial tiles, only lanes beyond the picture
+// (frames of a display size below the coded size: in_tile_edge, further down).
 // Only the bytes [plane + r pitch, plane + r pitch + row bytes) of a row are
 // read.  Host and device run the same in_tile (the CPU suite builds it into
 // tests/emu/libhl_ingest_emu.so).
@@ -232,16 +233,152 @@ inline void in_frame(const InFrame& F, const InCoef& C, int W, int H)
         for (int tx = 0; tx < (W >> 4); ++tx) in_tile<FMT>(F, C, W, tx, ty);
 }
 
+// ---- frames of a display size dW x dH below the coded size W x H -------------
+// (hl_amd_set_display_size: dW, dH even, W - 16 < dW <= W, H - 16 < dH <= H.)
+// The frame's planes have the rows and row bytes of dW x dH, and the coded
+// picture is the edge replication of the converted planes, through clamped
+// coordinates: luma (x, y) = the converted luma of source sample
+// (min(x, dW - 1), min(y, dH - 1)), chroma (bx, by) = the converted chroma of
+// source 2x2 block (min(bx, dW / 2 - 1), min(by, dH / 2 - 1)) -- for RGB that
+// block's SR, SG, SB through the arithmetic above.  A tile is full when
+// tx < (dW >> 4) and ty < (dH >> 1): in_tile as it is.  Every other tile of the
+// coded picture (at most one tile column and seven tile rows) is an edge tile:
+// in_tile_edge, which loads single bytes by clamped coordinate -- a 4-byte
+// word could cross the end of a row whose bytes are no multiple of 4 -- and
+// stores what in_tile stores.
+
+// tiles of a row pair and row pairs that are full
+constexpr int in_full_x(int dW) { return dW >> 4; }
+constexpr int in_full_y(int dH) { return dH >> 1; }
+// edge tiles of a picture: the right column's, then the bottom rows' left of it
+constexpr int in_edge_tiles(int W, int H, int dW, int dH)
+{
+    return ((W >> 4) - in_full_x(dW)) * (H >> 1) + in_full_x(dW) * ((H >> 1) - in_full_y(dH));
+}
+
+template <int FMT>
+HL_IN_HD void in_tile_edge(const InFrame& F, const InCoef& C, int W, int dW, int dH, int tx, int ty)
+{
+    static_assert(FMT >= 0 && FMT < IN_FORMATS, "HL_AMD_FORMAT_*");
+    uint32_t yo[2][4], uo[2], vo[2];
+    for (int j = 0; j < 4; ++j) yo[0][j] = yo[1][j] = 0;
+    uo[0] = uo[1] = vo[0] = vo[1] = 0;
+    const int cy = ty < (dH >> 1) ? ty : (dH >> 1) - 1;  // the source's chroma row (its row pair)
+    if constexpr (FMT == IN_I420 || FMT == IN_NV12) {
+        for (int r = 0; r < 2; ++r) {
+            const int y = 2 * ty + r < dH ? 2 * ty + r : dH - 1;
+            const uint8_t* py = F.plane[0] + (int64_t)y * F.pitch[0];
+            for (int k = 0; k < 16; ++k) {
+                const int x = 16 * tx + k < dW ? 16 * tx + k : dW - 1;
+                yo[r][k >> 2] |= (uint32_t)py[x] << (8 * (k & 3));
+            }
+        }
+        for (int b = 0; b < 8; ++b) {
+            const int cx = 8 * tx + b < (dW >> 1) ? 8 * tx + b : (dW >> 1) - 1;
+            uint32_t u, v;
+            if constexpr (FMT == IN_I420) {
+                u = (F.plane[1] + (int64_t)cy * F.pitch[1])[cx];
+                v = (F.plane[2] + (int64_t)cy * F.pitch[2])[cx];
+            }
+            else {
+                const uint8_t* pc = F.plane[1] + (int64_t)cy * F.pitch[1] + 2 * cx;
+                u = pc[0];
+                v = pc[1];
+            }
+            uo[b >> 2] |= u << (8 * (b & 3));
+            vo[b >> 2] |= v << (8 * (b & 3));
+        }
+    }
+    else {
+        const uint32_t ybias = (C.off << 16) + (1u << 15), cbias = (128u << 18) + (1u << 17);
+        const bool iny = ty < (dH >> 1);  // else both rows are the source's last row
+        for (int b = 0; b < 8; ++b) {     // the tile's 2x2 blocks, each from one source block
+            const bool inx = 8 * tx + b < (dW >> 1);  // else both columns are the source's last column
+            const int cx = inx ? 8 * tx + b : (dW >> 1) - 1;
+            uint32_t s[3] = {0, 0, 0}, yv[2][2];
+            for (int r = 0; r < 2; ++r)
+                for (int i = 0; i < 2; ++i) {
+                    const int x = 2 * cx + i;
+                    const int64_t row = (int64_t)(2 * cy + r);
+                    uint32_t R, G, B;
+                    if constexpr (FMT == IN_RGBP) {
+                        R = (F.plane[0] + row * F.pitch[0])[x];
+                        G = (F.plane[1] + row * F.pitch[1])[x];
+                        B = (F.plane[2] + row * F.pitch[2])[x];
+                    }
+                    else {
+                        const uint8_t* p = F.plane[0] + row * F.pitch[0] + (FMT == IN_RGBA32 ? 4 : 3) * x;
+                        R = p[0];
+                        G = p[1];
+                        B = p[2];
+                    }
+                    yv[r][i] = (C.y[0] * R + C.y[1] * G + C.y[2] * B + ybias) >> 16;
+                    s[0] += R;
+                    s[1] += G;
+                    s[2] += B;
+                }
+            for (int r = 0; r < 2; ++r)
+                for (int i = 0; i < 2; ++i) {
+                    const int k = 2 * b + i;
+                    yo[r][k >> 2] |= yv[iny ? r : 1][inx ? i : 1] << (8 * (k & 3));
+                }
+            const uint32_t u = (C.u[0] * s[0] + C.u[1] * s[1] + C.u[2] * s[2] + cbias) >> 18;
+            const uint32_t v = (C.v[0] * s[0] + C.v[1] * s[1] + C.v[2] * s[2] + cbias) >> 18;
+            uo[b >> 2] |= (u < 255u ? u : 255u) << (8 * (b & 3));
+            vo[b >> 2] |= (v < 255u ? v : 255u) << (8 * (b & 3));
+        }
+    }
+    uint8_t* dy = F.dst[0] + (size_t)(2 * ty) * W + 16 * tx;
+    in_store<4>(dy, yo[0]);
+    in_store<4>(dy + W, yo[1]);
+    in_store<2>(F.dst[1] + (size_t)ty * (W >> 1) + 8 * tx, uo);
+    in_store<2>(F.dst[2] + (size_t)ty * (W >> 1) + 8 * tx, vo);
+}
+
+// Edge tile i (< in_edge_tiles) of a picture: the right column's tiles row
+// pair by row pair, then the bottom rows' tiles left of that column
+HL_IN_HD void in_edge_at(int i, int W, int H, int dW, int dH, int* tx, int* ty)
+{
+    const int fx = in_full_x(dW), ex = (W >> 4) - fx, right = ex * (H >> 1);
+    if (i < right) {  // (ex = 1)
+        *tx = fx;
+        *ty = i;
+    }
+    else {  // (fx > 0: there are tiles left of the column)
+        const int j = i - right;
+        *ty = in_full_y(dH) + j / fx;
+        *tx = j - (j / fx) * fx;
+    }
+}
+
+// Every tile of one frame of the display size dW x dH into the coded W x H
+// planes: the full tiles, then the edge tiles in the order of the kernel's lanes
+template <int FMT>
+inline void in_frame_display(const InFrame& F, const InCoef& C, int W, int H, int dW, int dH)
+{
+    for (int ty = 0; ty < in_full_y(dH); ++ty)
+        for (int tx = 0; tx < in_full_x(dW); ++tx) in_tile<FMT>(F, C, W, tx, ty);
+    for (int i = 0; i < in_edge_tiles(W, H, dW, dH); ++i) {
+        int tx, ty;
+        in_edge_at(i, W, H, dW, dH, &tx, &ty);
+        in_tile_edge<FMT>(F, C, W, dW, dH, tx, ty);
+    }
+}
+
 #if defined(__HIPCC__)
 // One launch for every frame (grid z) of one format.
 struct InArgs {
     InFrame one;         // the one frame, when tab is null
     const InFrame* tab;  // else the launch's frames (device memory)
     InCoef coef;         // RGB formats
-    int32_t W, H;
+    int32_t W, H;        // the coded size: the destination planes'
+    int32_t dW, dH;      // the frames' size (the display size); 0, 0 = W, H
 };
 
-// `frames` frames of format fmt on `stream`
+constexpr int kInEdgeLanes = 64;  // lanes of a workgroup of k_ingest_edge: one edge tile each
+
+// `frames` frames of format fmt on `stream`: k_ingest on the full tiles and,
+// for frames below the coded size, k_ingest_edge on the others
 hipError_t launch_ingest(const InArgs& A, int fmt, int frames, hipStream_t stream);
 
 #if defined(HL_INGEST_KERNELS)  // hl_ingest.hip: the one translation unit that holds the kernels
@@ -249,7 +386,7 @@ template <int FMT>
 __global__ __launch_bounds__(kInLanesX * kInLanesY) void k_ingest(InArgs A)
 {
     const int tx = blockIdx.x * kInLanesX + threadIdx.x, ty = blockIdx.y * kInLanesY + threadIdx.y;
-    if (tx >= (A.W >> 4) || ty >= (A.H >> 1)) return;  // lanes beyond the picture
+    if (tx >= (A.dW >> 4) || ty >= (A.dH >> 1)) return;  // lanes beyond the full tiles (the picture's, without a display size)
     if (A.tab) {
         const InFrame F = A.tab[blockIdx.z];
         in_tile<FMT>(F, A.coef, A.W, tx, ty);
@@ -257,17 +394,51 @@ __global__ __launch_bounds__(kInLanesX * kInLanesY) void k_ingest(InArgs A)
     else in_tile<FMT>(A.one, A.coef, A.W, tx, ty);
 }
 
-hipError_t launch_ingest(const InArgs& A, int fmt, int frames, hipStream_t stream)
+// the edge tiles of every frame (grid z), one lane each
+template <int FMT>
+__global__ __launch_bounds__(kInEdgeLanes) void k_ingest_edge(InArgs A)
 {
-    if (fmt < 0 || fmt >= IN_FORMATS || frames < 1 || frames > 65535 || A.W <= 0 || A.H <= 0 || (A.W & 15) || (A.H & 15))
+    const int i = blockIdx.x * kInEdgeLanes + threadIdx.x;
+    if (i >= in_edge_tiles(A.W, A.H, A.dW, A.dH)) return;  // lanes beyond the edge tiles
+    int tx, ty;
+    in_edge_at(i, A.W, A.H, A.dW, A.dH, &tx, &ty);
+    if (A.tab) {
+        const InFrame F = A.tab[blockIdx.z];
+        in_tile_edge<FMT>(F, A.coef, A.W, A.dW, A.dH, tx, ty);
+    }
+    else in_tile_edge<FMT>(A.one, A.coef, A.W, A.dW, A.dH, tx, ty);
+}
+
+hipError_t launch_ingest(const InArgs& A0, int fmt, int frames, hipStream_t stream)
+{
+    InArgs A = A0;
+    if (!A.dW && !A.dH) {
+        A.dW = A.W;
+        A.dH = A.H;
+    }
+    if (fmt < 0 || fmt >= IN_FORMATS || frames < 1 || frames > 65535 || A.W <= 0 || A.H <= 0 || (A.W & 15) || (A.H & 15) || ((A.dW | A.dH) & 1) ||
+        A.dW <= A.W - 16 || A.dW > A.W || A.dH <= A.H - 16 || A.dH > A.H || A.dW <= 0 || A.dH <= 0)
         return hipErrorInvalidValue;
-    const dim3 block(kInLanesX, kInLanesY);
-    const dim3 grid(((A.W >> 4) + kInLanesX - 1) / kInLanesX, ((A.H >> 1) + kInLanesY - 1) / kInLanesY, frames);
-    if (fmt == IN_I420) k_ingest<IN_I420><<<grid, block, 0, stream>>>(A);
-    else if (fmt == IN_NV12) k_ingest<IN_NV12><<<grid, block, 0, stream>>>(A);
-    else if (fmt == IN_RGB24) k_ingest<IN_RGB24><<<grid, block, 0, stream>>>(A);
-    else if (fmt == IN_RGBA32) k_ingest<IN_RGBA32><<<grid, block, 0, stream>>>(A);
-    else k_ingest<IN_RGBP><<<grid, block, 0, stream>>>(A);
+    if (in_full_x(A.dW) > 0) {  // (dH >= 2: a full row pair)
+        const dim3 block(kInLanesX, kInLanesY);
+        const dim3 grid((in_full_x(A.dW) + kInLanesX - 1) / kInLanesX, (in_full_y(A.dH) + kInLanesY - 1) / kInLanesY, frames);
+        if (fmt == IN_I420) k_ingest<IN_I420><<<grid, block, 0, stream>>>(A);
+        else if (fmt == IN_NV12) k_ingest<IN_NV12><<<grid, block, 0, stream>>>(A);
+        else if (fmt == IN_RGB24) k_ingest<IN_RGB24><<<grid, block, 0, stream>>>(A);
+        else if (fmt == IN_RGBA32) k_ingest<IN_RGBA32><<<grid, block, 0, stream>>>(A);
+        else k_ingest<IN_RGBP><<<grid, block, 0, stream>>>(A);
+        const hipError_t rc = hipGetLastError();
+        if (rc != hipSuccess) return rc;
+    }
+    const int edge = in_edge_tiles(A.W, A.H, A.dW, A.dH);
+    if (edge > 0) {
+        const dim3 grid((edge + kInEdgeLanes - 1) / kInEdgeLanes, 1, frames);
+        if (fmt == IN_I420) k_ingest_edge<IN_I420><<<grid, kInEdgeLanes, 0, stream>>>(A);
+        else if (fmt == IN_NV12) k_ingest_edge<IN_NV12><<<grid, kInEdgeLanes, 0, stream>>>(A);
+        else if (fmt == IN_RGB24) k_ingest_edge<IN_RGB24><<<grid, kInEdgeLanes, 0, stream>>>(A);
+        else if (fmt == IN_RGBA32) k_ingest_edge<IN_RGBA32><<<grid, kInEdgeLanes, 0, stream>>>(A);
+        else k_ingest_edge<IN_RGBP><<<grid, kInEdgeLanes, 0, stream>>>(A);
+    }
     return hipGetLastError();
 }
 #endif  // HL_INGEST_KERNELS

@@ -1,4 +1,4 @@
-// hl_ingest.hip -- k_ingest (hl_ingest.h) in a translation unit of its own.
+// hl_ingest.hip -- k_ingest and k_ingest_edge (hl_ingest.h) in a translation unit of their own.
 // It is compiled without the product's device scheduling flag: under
 // -amdgpu-sched-strategy=iterative-ilp the register allocator of the ROCm 7.2
 // compiler crashes on the planar-RGB kernel (VirtRegAuxInfo::isRematerializable),

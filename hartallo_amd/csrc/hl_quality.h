@@ -35,8 +35,18 @@
 // their lanes' sums with shuffles, and lane 0 of the workgroup adds the two
 // totals into the picture's sums with integer atomicAdd (exact in any order).
 //
+// With a display size (hl_amd_set_display_size) only the display rectangle of
+// each plane is measured, a window of ww x wh samples at the plane's top left
+// (dW x dH of luma, dW / 2 x dH / 2 of chroma: any size, odd ones too).  The
+// strips are loaded as ever and the bytes of a strip outside the window are
+// zeroed in both pictures (q_mask: a byte mask on the two words of a row, a
+// zero row beyond the window), so every block sum, the SSE and the per-
+// macroblock SSE are those of the window's samples without a second code
+// path; the 8x8 windows counted are those wholly inside, (bx, by) with
+// bx <= ww/4 - 2, by <= wh/4 - 2.  Without a display size no mask is applied.
+//
 // Host and device run the same per-strip and per-window code (the CPU suite
-// builds it into tests/emu/libhl_quality_emu.so).
+// builds it into tests/emu/libhl_quality_emu.so and libhl_display_emu.so).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -157,11 +167,37 @@ HL_Q_HD uint32_t q_mb_sse(const uint32_t* s1, const uint32_t* s2, int mx, int my
     return q_sse(ss, s12);
 }
 
+// The bytes of sample row y of a strip at column x that lie inside the window
+// of ww x wh samples (the plane's top-left rectangle), as masks of the row's
+// two words; both 0 for a row beyond the window
+HL_Q_HD void q_mask(int x, int y, int ww, int wh, uint32_t* lo, uint32_t* hi)
+{
+    const int left = ww - x, nv = y < wh ? (left < 0 ? 0 : left > 8 ? 8 : left) : 0;
+    *lo = nv >= 4 ? 0xFFFFFFFFu : (1u << (8 * nv)) - 1u;
+    *hi = nv <= 4 ? 0u : nv >= 8 ? 0xFFFFFFFFu : (1u << (8 * (nv - 4))) - 1u;
+}
+
+// the first sample of strip i of the tile whose first block is (bx0, by0)
+HL_Q_HD void q_strip_xy(int i, int bx0, int by0, int* x, int* y)
+{
+    const int r = i / kQStripsX, c = i - r * kQStripsX;
+    *x = 4 * bx0 + 8 * c;
+    *y = 4 * (by0 + r);
+}
+
+// 8x8 windows (stride 4) that lie wholly inside a plane or window of w x h samples
+constexpr uint64_t q_windows(int w, int h) { return (uint64_t)(w / 4 > 1 ? w / 4 - 1 : 0) * (uint64_t)(h / 4 > 1 ? h / 4 - 1 : 0); }
+
 // One plane pair on the host, tile by tile as the kernel's workgroups take it
-// (the same staging indices, the same per-strip and per-window code):
+// (the same staging indices, the same per-strip and per-window code), measured
+// over the window of ww x wh samples at the plane's top left (any size from
+// 1 x 1 to W x H): the bytes of a loaded strip outside the window are zeroed in
+// both pictures, so every sum is that of the window's samples, and the 8x8
+// windows counted are those wholly inside it.
 // *sse += sum (a - b)^2, *ssim += sum Q; mb (or null) = the SSE of every 16x16
-// macroblock (W, H multiples of 16 then).
-inline void quality_plane_host(const uint8_t* a, const uint8_t* b, int W, int H, uint64_t* sse, int64_t* ssim, uint32_t* mb)
+// macroblock's part inside the window (W, H multiples of 16 then).
+inline void quality_plane_window_host(const uint8_t* a, const uint8_t* b, int W, int H, int ww, int wh, uint64_t* sse, int64_t* ssim,
+                                      uint32_t* mb)
 {
     uint32_t s[3][kQRows * kQLdsW];
     for (int by0 = 0; 4 * by0 < H; by0 += kQTileBY)
@@ -171,10 +207,18 @@ inline void quality_plane_host(const uint8_t* a, const uint8_t* b, int W, int H,
                 ptrdiff_t off;
                 bool own;
                 const int at = q_strip(i, bx0, by0, W, H, &off, &own);
+                int x, y;
+                q_strip_xy(i, bx0, by0, &x, &y);
                 uint32_t va[4][2] = {}, vb[4][2] = {};
                 for (int r = 0; r < 4 && off >= 0; ++r) {
+                    uint32_t m[2];
+                    q_mask(x, y + r, ww, wh, &m[0], &m[1]);
                     memcpy(va[r], a + off + (ptrdiff_t)r * W, 8);
                     memcpy(vb[r], b + off + (ptrdiff_t)r * W, 8);
+                    for (int h = 0; h < 2; ++h) {
+                        va[r][h] &= m[h];
+                        vb[r][h] &= m[h];
+                    }
                 }
                 for (int h = 0; h < 2; ++h) {
                     const uint32_t ra[4] = {va[0][h], va[1][h], va[2][h], va[3][h]}, rb[4] = {vb[0][h], vb[1][h], vb[2][h], vb[3][h]};
@@ -186,13 +230,19 @@ inline void quality_plane_host(const uint8_t* a, const uint8_t* b, int W, int H,
             }
             for (int w = 0; w < kQTileBX * kQTileBY; ++w) {
                 const int wx = w % kQTileBX, wy = w / kQTileBX;
-                if (bx0 + wx <= W / 4 - 2 && by0 + wy <= H / 4 - 2) *ssim += q_window_at(s[0], s[1], s[2], wx, wy);
+                if (bx0 + wx <= ww / 4 - 2 && by0 + wy <= wh / 4 - 2) *ssim += q_window_at(s[0], s[1], s[2], wx, wy);
             }
             for (int m = 0; mb && m < 32; ++m) {
                 const int mbx = bx0 / 4 + (m & 15), mby = by0 / 4 + (m >> 4);
                 if (mbx < W / 16 && mby < H / 16) mb[(size_t)mby * (W / 16) + mbx] = q_mb_sse(s[1], s[2], m & 15, m >> 4);
             }
         }
+}
+
+// the whole plane (the window is the plane: every mask is all ones)
+inline void quality_plane_host(const uint8_t* a, const uint8_t* b, int W, int H, uint64_t* sse, int64_t* ssim, uint32_t* mb)
+{
+    quality_plane_window_host(a, b, W, H, W, H, sse, ssim, mb);
 }
 
 #if defined(__HIPCC__)
@@ -203,6 +253,7 @@ struct QualityArgs {
     unsigned long long* sums;      // [pictures][3][2] sse, ssim_q30 (two's complement), zeroed before the launch
     uint32_t* mb;                  // [pictures][(W / 16)(H / 16)] luma SSE per macroblock
     int32_t W, H;                  // the luma size, multiples of 16; planes dense, 8-byte aligned
+    int32_t dW, dH;                // the luma window measured (the display size, even), 0, 0: the whole picture
 };
 
 __global__ __launch_bounds__(256) void k_quality(QualityArgs A)
@@ -222,6 +273,9 @@ __global__ __launch_bounds__(256) void k_quality(QualityArgs A)
         src = plane == 0 ? A.one[0] : plane == 1 ? A.one[1] : A.one[2];
         rec = plane == 0 ? A.one[3] : plane == 1 ? A.one[4] : A.one[5];
     }
+    // the window measured: the plane's top-left ww x wh samples (the plane itself without a display size)
+    const bool windowed = A.dW != 0;
+    const int ww = windowed ? (plane ? A.dW >> 1 : A.dW) : W, wh = windowed ? (plane ? A.dH >> 1 : A.dH) : H;
     const int t = (int)threadIdx.x;
     uint2 va[2][4], vb[2][4];
     int at[2];
@@ -241,6 +295,19 @@ __global__ __launch_bounds__(256) void k_quality(QualityArgs A)
                 for (int r = 0; r < 4; ++r) {
                     va[j][r] = *reinterpret_cast<const uint2*>(src + off + (ptrdiff_t)r * W);
                     vb[j][r] = *reinterpret_cast<const uint2*>(rec + off + (ptrdiff_t)r * W);
+                }
+                if (windowed) {  // what lies outside the window is zero in both pictures: every sum is the window's
+                    int x, y;
+                    q_strip_xy(i, bx0, by0, &x, &y);
+                    HL_Q_UNROLL
+                    for (int r = 0; r < 4; ++r) {
+                        uint32_t lo, hi;
+                        q_mask(x, y + r, ww, wh, &lo, &hi);
+                        va[j][r].x &= lo;
+                        va[j][r].y &= hi;
+                        vb[j][r].x &= lo;
+                        vb[j][r].y &= hi;
+                    }
                 }
             }
         }
@@ -263,7 +330,7 @@ __global__ __launch_bounds__(256) void k_quality(QualityArgs A)
     HL_Q_UNROLL
     for (int j = 0; j < 2; ++j) {
         const int w = t + 256 * j, wx = w & (kQTileBX - 1), wy = w / kQTileBX;
-        if (bx0 + wx <= W / 4 - 2 && by0 + wy <= H / 4 - 2) ssim += q_window_at(s_b[0], s_b[1], s_b[2], wx, wy);
+        if (bx0 + wx <= ww / 4 - 2 && by0 + wy <= wh / 4 - 2) ssim += q_window_at(s_b[0], s_b[1], s_b[2], wx, wy);
     }
     if (plane == 0 && t < 32) {
         const int mbw = W >> 4, mbx = (bx0 >> 2) + (t & 15), mby = (by0 >> 2) + (t >> 4);
@@ -292,6 +359,7 @@ inline hipError_t launch_quality(const QualityArgs& A, int pictures, hipStream_t
 {
     if (pictures < 1 || pictures > 65535 / 3 || A.W <= 0 || A.H <= 0 || (A.W & 15) || (A.H & 15) || (A.H + 31) / 32 > 65535 || !A.sums || !A.mb)
         return hipErrorInvalidValue;
+    if ((A.dW || A.dH) && (((A.dW | A.dH) & 1) || A.dW <= 0 || A.dW > A.W || A.dH <= 0 || A.dH > A.H)) return hipErrorInvalidValue;
     for (int c = 0; c < 6 && !A.tab; ++c)
         if (!A.one[c]) return hipErrorInvalidValue;
     const dim3 grid((A.W + 4 * kQTileBX - 1) / (4 * kQTileBX), (A.H + 4 * kQTileBY - 1) / (4 * kQTileBY), 3 * pictures);

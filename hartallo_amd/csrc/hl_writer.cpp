@@ -213,6 +213,34 @@ size_t put_nal(uint8_t* out, size_t cap, const uint8_t* rbsp, size_t n)
     return n + 3;
 }
 
+// the same with standard emulation prevention of the payload (the bytes after
+// the NAL header): 03 goes before every byte <= 3 that follows two zero bytes
+// of the escaped stream, and after a payload that ends in a zero byte
+size_t put_nal_escaped(uint8_t* out, size_t cap, const uint8_t* nal, size_t n)
+{
+    if (cap < 4 || n < 1) return 0;
+    size_t k = 0, zeros = 0;
+    out[k++] = 0;
+    out[k++] = 0;
+    out[k++] = 1;
+    out[k++] = nal[0];
+    for (size_t i = 1; i < n; ++i) {
+        if (zeros >= 2 && nal[i] <= 3) {
+            if (k >= cap) return 0;
+            out[k++] = 3;
+            zeros = 0;
+        }
+        if (k >= cap) return 0;
+        out[k++] = nal[i];
+        zeros = nal[i] ? 0 : zeros + 1;
+    }
+    if (n > 1 && nal[n - 1] == 0) {  // (an RBSP ends in its stop bit: never here)
+        if (k >= cap) return 0;
+        out[k++] = 3;
+    }
+    return k;
+}
+
 }  // namespace
 
 int sps_max_num_ref_frames(int width, int height, int max_ref_frame)
@@ -257,10 +285,19 @@ size_t write_stream_headers(const StreamParams& p, uint8_t* out, size_t cap)
         bw.ue((uint32_t)(p.height / 16 - 1));
         bw.u1(1);  // frame_mbs_only_flag
         bw.u1(0);  // direct_8x8_inference_flag
-        bw.u1(0);  // frame_cropping_flag
+        // frame_cropping_flag: 0 as the reference writes it (sps.c:625) unless
+        // a display size below the coded size is set (no reference interface)
+        const bool crop = p.display_width > 0 && p.display_height > 0 && (p.display_width != p.width || p.display_height != p.height);
+        bw.u1(crop ? 1 : 0);
+        if (crop) {
+            bw.ue(0);                                              // frame_crop_left_offset
+            bw.ue((uint32_t)((p.width - p.display_width) / 2));    // frame_crop_right_offset (CropUnitX = 2)
+            bw.ue(0);                                              // frame_crop_top_offset
+            bw.ue((uint32_t)((p.height - p.display_height) / 2));  // frame_crop_bottom_offset (CropUnitY = 2)
+        }
         bw.u1(0);  // vui_parameters_present_flag
         bw.trailing();
-        n += put_nal(out + n, cap - n, buf, bw.bytes());
+        n += put_nal_escaped(out + n, cap - n, buf, bw.bytes());
     }
     {
         memset(buf, 0, sizeof(buf));

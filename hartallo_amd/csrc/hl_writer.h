@@ -16,7 +16,17 @@ namespace hl {
 struct StreamParams {
     int32_t width, height, qp, deblock;
     int32_t max_ref_frame = 1;  // hl_codec_t.max_ref_frame (hl_codec.c:36 default 1): SPS/PPS only
+    // the display size (hl_amd_set_display_size): SPS cropping fields only;
+    // 0 x 0, or the coded size itself: none (the reference's SPS, sps.c:625)
+    int32_t display_width = 0, display_height = 0;
 };
+
+// is dw x dh a display size of a coded w x h picture: even, and within the
+// last macroblock column and row (w - 16 < dw <= w, h - 16 < dh <= h)
+inline bool display_size_ok(int w, int h, int dw, int dh)
+{
+    return !((dw | dh) & 1) && dw > w - 16 && dw <= w && dh > h - 16 && dh <= h && dw > 0 && dh > 0;
+}
 
 // max_num_ref_frames the reference writes in a SPS of this picture size:
 // min(MaxDpbMbs / PicSizeInMbs, max_ref_frame) (sps.c:620-636, the level
@@ -48,7 +58,12 @@ private:
 // Writes the 00 00 01-prefixed SPS and PPS NAL units; returns bytes written.
 // The PPS's num_ref_idx_l0_default_active_minus1 follows the SPS's
 // max_num_ref_frames (pps.c:291); P slices still override it to one active
-// reference (slice.c:289, encode.c:269).
+// reference (slice.c:289, encode.c:269).  With a display size below the coded
+// size the SPS carries frame_cropping_flag = 1 and the offsets left 0, right
+// (width - display_width) / 2, top 0, bottom (height - display_height) / 2 (in
+// units of two luma samples: 4:2:0, frame_mbs_only), and nothing else changes.
+// The SPS payload gets emulation prevention (00 00 03 before a byte <= 3 that
+// follows two zero bytes); no SPS of a picture up to 2048 x 2048 needs it.
 size_t write_stream_headers(const StreamParams& p, uint8_t* out, size_t cap);
 
 struct SliceState {

@@ -228,6 +228,53 @@ int32_t hl_amd_set_rate_control(hl_amd_encoder_t* encoder, int64_t bitrate, int3
  * reads it when it builds the first SPS), else HL_AMD_ERROR_INVALID_STATE. */
 int32_t hl_amd_set_max_ref_frame(hl_amd_encoder_t* encoder, int32_t max_ref_frame);
 
+/* ---- pictures of any even size: the display size ----
+ * No reference interface: the reference refuses pictures that are no
+ * multiples of 16 (hl_codec_264.c:430-433) and always writes
+ * frame_cropping_flag = 0 (hl_codec_264_sps.c:625).  The encoder is created
+ * at the coded size W x H (multiples of 16, as ever); the display size dw x dh
+ * -- both even, W - 16 < dw <= W, H - 16 < dh <= H, else
+ * HL_AMD_ERROR_INVALID_PARAMETER -- is what a decoder shows: the SPS then
+ * carries frame_cropping_flag = 1 with the offsets left 0, right (W - dw) / 2,
+ * top 0, bottom (H - dh) / 2 (units of two luma samples), and every other
+ * field, level_idc and max_num_ref_frames included, stays the reference's for
+ * W x H.  The PPS and every slice NAL are the reference's for the coded
+ * picture, byte for byte.  (W, H) means none: today's headers.  Off by
+ * default; it changes no byte of a stream coded without it.
+ * Which call takes which size:
+ *   - hl_amd_encode, _device, _batch, _streams and their _ex forms keep taking
+ *     planes of the coded size that the caller padded;
+ *   - hl_amd_encode_frame and hl_amd_encode_frames take frames of the display
+ *     size (rows and row bytes follow dw and dh) and the encoder pads them to
+ *     W x H on the GPU by edge replication of the converted planes, defined
+ *     through clamped coordinates: luma sample (x, y) is the converted luma of
+ *     source sample (min(x, dw - 1), min(y, dh - 1)), chroma sample (bx, by)
+ *     the converted chroma of source 2x2 block (min(bx, dw/2 - 1),
+ *     min(by, dh/2 - 1)) -- for RGB that block's SR, SG, SB through the
+ *     arithmetic below.  Scene-cut detection reads the padded planes;
+ *   - hl_amd_get_input, hl_amd_get_recon and the debug calls return planes of
+ *     the coded size (no cropping is applied to them);
+ *   - quality (hl_amd_set_quality) measures the display rectangle only: dw x dh
+ *     of luma, dw/2 x dh/2 of chroma (see there).
+ * Like hl_amd_set_max_ref_frame it is part of the SPS: accepted only before
+ * the first picture and with nothing queued in the look-ahead, else
+ * HL_AMD_ERROR_INVALID_STATE; the two setters work in either order.  Encoders
+ * with spatial layers: HL_AMD_ERROR_NOT_IMPLEMENTED, and hl_amd_add_layer
+ * after a display size was set returns the same.  Not served: left and top
+ * offsets, odd sizes, a VUI. */
+int32_t hl_amd_set_display_size(hl_amd_encoder_t* encoder, int32_t width, int32_t height);
+/* the display size (the coded size when none was set) */
+int32_t hl_amd_get_display_size(hl_amd_encoder_t* encoder, int32_t* width, int32_t* height);
+
+/* The SPS and PPS ("00 00 01"-prefixed) that an encoder created with these
+ * parameters (width, height and qp are read) emits after
+ * hl_amd_set_max_ref_frame(max_ref_frame) and hl_amd_set_display_size(
+ * display_width, display_height) -- (width, height) for no cropping.  A pure
+ * function (no device).  Returns the bytes written, or 0 when a setting is
+ * refused or the bytes do not fit in cap. */
+size_t hl_amd_stream_headers(const hl_amd_params_t* params, int32_t max_ref_frame, int32_t display_width, int32_t display_height,
+                             uint8_t* out, size_t cap);
+
 /* SliceQPY of the last encoded picture (the rate-controlled QP), or -1 */
 int32_t hl_amd_last_qp(hl_amd_encoder_t* encoder);
 
@@ -519,7 +566,14 @@ int32_t hl_amd_bench_scene(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
  *     S1 = sum a, S2 = sum b, SS = sum (a^2 + b^2), S12 = sum a b of the window,
  *     num = (2 S1 S2 + 416)(2 (64 S12 - S1 S2) + 235963),
  *     den = (S1^2 + S2^2 + 416)(64 SS - S1^2 - S2^2 + 235963).
- * hl_amd_psnr_db and hl_amd_ssim_mean turn them into the usual figures. */
+ * hl_amd_psnr_db and hl_amd_ssim_mean turn them into the usual figures.
+ * With a display size (hl_amd_set_display_size) "the plane" above is the
+ * plane's display rectangle, w x h = dw x dh of luma and dw/2 x dh/2 of chroma
+ * (odd sizes and sizes that are no multiples of 4 included): samples[c] = w h,
+ * sse[c] runs over its samples, ssim_q30[c] over the 8x8 windows at stride 4
+ * that lie wholly inside it, windows[c] = max(0, w/4 - 1) max(0, h/4 - 1)
+ * (integer divisions), and hl_amd_debug_quality_mb gives the SSE of each
+ * macroblock's display part.  Without one every result is what it was. */
 typedef struct hl_amd_quality_s {
     uint64_t sse[3], samples[3];
     int64_t ssim_q30[3];
@@ -588,8 +642,13 @@ double hl_amd_ssim_mean(int64_t q30, uint64_t windows);
  *     Grey input gives U = V = 128 exactly.  The default is BT.601 limited.
  *     The stream carries no VUI colour description (the reference writes
  *     none): which matrix was used travels out of band.
- * Picture sizes stay multiples of 16; spatial layers are not served
- * (HL_AMD_ERROR_NOT_IMPLEMENTED). */
+ * The coded size stays a multiple of 16.  With a display size
+ * (hl_amd_set_display_size) W and H above are the display size dw x dh: the
+ * frames have its rows and row bytes, and a second kernel (k_ingest_edge, one
+ * lane per tile of 16 x 2 samples that is not wholly inside the frame: at most
+ * one tile column and seven tile rows) pads the planes to the coded size by
+ * the edge replication defined there, loading single bytes by clamped
+ * coordinate.  Spatial layers are not served (HL_AMD_ERROR_NOT_IMPLEMENTED). */
 enum {
     HL_AMD_FORMAT_I420 = 0,
     HL_AMD_FORMAT_NV12,
@@ -611,11 +670,15 @@ typedef struct hl_amd_frame_s {
  * leaves the encoder as it was and the next call continues the stream.
  * HL_AMD_ERROR_INVALID_PARAMETER: an unknown format; a null plane the format
  * needs; a pitch that is negative, or non-zero and below row bytes; a device
- * plane or pitch that is no multiple of 4 (k_ingest loads 4-byte words).
+ * plane or pitch that is no multiple of 4 (k_ingest loads 4-byte words; a
+ * pitch of 0 counts as the row bytes, so a dense device frame of a display
+ * width like 34 is refused, while any even width works from the host, whose
+ * rows are staged with a pitch rounded up to a multiple of 4).
  * HL_AMD_ERROR_NOT_IMPLEMENTED: an encoder with spatial layers.  The ctl is
  * checked as in the _ex calls.  HL_AMD_ERROR_INVALID_STATE: an encoder that
  * an earlier GPU failure has left unusable.
- * A dense I420 frame in device memory (every pitch 0 or row bytes) is
+ * A dense I420 frame in device memory (every pitch 0 or row bytes) of the
+ * coded size (no display size below it is set) is
  * forwarded untouched -- no copy, no kernel: it is hl_amd_encode_device_ex's
  * frame, the 4-byte rule does not apply to it, and the alignment rules of
  * scene-cut detection and quality apply to the caller's planes as there.
