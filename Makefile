@@ -6,6 +6,8 @@
 #   tests/emu/libhl_quality_emu.so   test-only host build of the quality metric (hl_quality.h)
 #   tests/emu/libhl_ingest_emu.so    test-only host build of the frame ingest (hl_ingest.h)
 #   tests/emu/libhl_display_emu.so   test-only host build of the display size's edge tiles and quality window (hl_ingest.h, hl_quality.h)
+#   tests/emu/libhl_svc_display_emu.so  test-only host build of the ingest's edge tiles with margins wider than a macroblock (hl_ingest.h)
+#   tests/emu/libhl_svc_geom_emu.so  test-only host exports of the enhancement layers' constants and Intra_Base sample (hl_svc.h)
 #   tests/emu/libhl_sched_emu.so     test-only host build of the pipelined run's pop (hl_sched.h)
 #   tests/emu/libhl_rec_emu.so       test-only host exports of the candidate record's pack / unpack (hl_mbcore.h)
 #   tests/gpu_unit/libhl_unit.so     test-only GPU unit kernels (coop pipeline vs scalar primitives)
@@ -35,7 +37,7 @@ INGOBJ  := build/obj/hl_ingest.o
 all: product emu unit oracle sanitize
 
 product: hartallo_amd/libhartallo_amd.so
-emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_display_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so
+emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_display_emu.so tests/emu/libhl_svc_display_emu.so tests/emu/libhl_svc_geom_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so
 unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so
 
 $(INGOBJ): $(CSRC)/hl_ingest.hip $(CSRC)/hl_ingest.h
@@ -73,6 +75,14 @@ tests/emu/libhl_ingest_emu.so: tests/emu/hl_ingest_emu.cpp $(CSRC)/hl_ingest.h
 tests/emu/libhl_display_emu.so: tests/emu/hl_display_emu.cpp $(CSRC)/hl_ingest.h $(CSRC)/hl_quality.h
 	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_display_emu.cpp
 
+# the access unit's display size on the host: the ingest's tiles with margins up to (16 << K) - 2 (no device code)
+tests/emu/libhl_svc_display_emu.so: tests/emu/hl_svc_display_emu.cpp $(CSRC)/hl_ingest.h
+	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_svc_display_emu.cpp
+
+# the enhancement layers' per-layer constants and Intra_Base luma sample on the host (hl_filters.h brings its kernels along, as in libhl_emu.so)
+tests/emu/libhl_svc_geom_emu.so: tests/emu/hl_svc_geom_emu.hip $(CSRC)/hl_writer.cpp $(HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -O2 -shared -o $@ tests/emu/hl_svc_geom_emu.hip $(CSRC)/hl_writer.cpp
+
 # the pop's key, choice, head rule and slot / claim transitions on the host (no device code)
 tests/emu/libhl_sched_emu.so: tests/emu/hl_sched_emu.cpp $(CSRC)/hl_sched.h
 	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_sched_emu.cpp
@@ -105,11 +115,13 @@ tests/gpu_unit/libhl_unit_rec.so: tests/gpu_unit/hl_unit_rec.hip $(HDRS)
 #       program carries the sanitizers' runtimes itself)
 #   tests/sanitize/ingest_edge_asan  the same for frames of a display size below
 #       the coded size: the full tiles and the edge tiles (in_tile_edge)
+#   tests/sanitize/ingest_wide_asan  the same for the top layer of an encoder
+#       with spatial layers: margins up to (16 << K) - 2, several edge tile columns
 # (hipcc: every -fsanitize= directly after -Xarch_host, host code only)
 SANFLAGS := -std=c++17 -O1 -g -fno-omit-frame-pointer -fPIC -ffp-contract=off -Wno-unused-function -Wno-unused-variable
 ASAN := -Xarch_host -fsanitize=address
 UBSAN := -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined
-sanitize: tests/sanitize/libhl_emu_asan.so tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan tests/sanitize/ingest_edge_asan
+sanitize: tests/sanitize/libhl_emu_asan.so tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan tests/sanitize/ingest_edge_asan tests/sanitize/ingest_wide_asan
 tests/sanitize/hl_writer_asan.o: $(CSRC)/hl_writer.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) $(ASAN) $(UBSAN) -c -o $@ $<
 tests/sanitize/hl_rc_asan.o: $(CSRC)/hl_rc.cpp $(HDRS)
@@ -126,6 +138,8 @@ tests/sanitize/ingest_asan: tests/sanitize/ingest_asan.cpp $(CSRC)/hl_ingest.h
 	$(HIPCC) $(SANFLAGS) $(ASAN) $(UBSAN) -o $@ -x c++ tests/sanitize/ingest_asan.cpp
 tests/sanitize/ingest_edge_asan: tests/sanitize/ingest_edge_asan.cpp $(CSRC)/hl_ingest.h
 	$(HIPCC) $(SANFLAGS) $(ASAN) $(UBSAN) -o $@ -x c++ tests/sanitize/ingest_edge_asan.cpp
+tests/sanitize/ingest_wide_asan: tests/sanitize/ingest_wide_asan.cpp $(CSRC)/hl_ingest.h
+	$(HIPCC) $(SANFLAGS) $(ASAN) $(UBSAN) -o $@ -x c++ tests/sanitize/ingest_wide_asan.cpp
 # the emulator under UndefinedBehaviorSanitizer too: a 16-minute compile of
 # the kernel logic, run once per change of the shift / overflow idioms
 # (DESIGN.md §2); tests/test_sanitizers.py uses it when it is present
@@ -168,5 +182,5 @@ oracle: product  # oracle/_ref/drop_in_enc links the product library
 	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
-	rm -f $(INGOBJ) hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_display_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan tests/sanitize/ingest_edge_asan
+	rm -f $(INGOBJ) hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_display_emu.so tests/emu/libhl_svc_display_emu.so tests/emu/libhl_svc_geom_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan tests/sanitize/ingest_edge_asan tests/sanitize/ingest_wide_asan
 	$(MAKE) -C oracle clean

@@ -115,6 +115,11 @@ EXPORTED_SYMBOLS = (
     "hl_amd_encode_frames",
     "hl_amd_get_input",
     "hl_amd_bench_ingest",
+    "hl_amd_set_au_display_size",
+    "hl_amd_get_au_display_size",
+    "hl_amd_svc_stream_headers",
+    "hl_amd_encode_au_frame",
+    "hl_amd_encode_au_frames",
     "hl_amd_version",
 )
 
@@ -370,6 +375,24 @@ def stream_headers(width: int, height: int, qp: int = 28, max_ref_frame: int = 1
     return buf.raw[:n]
 
 
+def svc_stream_headers(width: int, height: int, layers: int, qp: int = 28, max_ref_frame: int = 1, display_width: "int | None" = None,
+                       display_height: "int | None" = None) -> bytes:
+    """Every header NAL unit (SPS 0, the subset SPSs, the PPSs, with start
+    codes) of an SvcEncoder(width, height, layers) -- width x height is the
+    base layer -- after set_max_ref_frame(max_ref_frame) and
+    set_au_display_size(display_width, display_height) -- None: the top coded
+    size, no cropping (hl_amd_svc_stream_headers; no device).  ValueError for
+    settings an encoder refuses."""
+    p = _Params(width, height, qp, 16, 1, 30, 0, 0)
+    buf = ctypes.create_string_buffer(1024)
+    k = layers - 1
+    n = load_library().hl_amd_svc_stream_headers(ctypes.byref(p), max_ref_frame, layers, (width << k) if display_width is None else display_width,
+                                                 (height << k) if display_height is None else display_height, buf, len(buf))
+    if not n:
+        raise ValueError("svc_stream_headers: a size or setting the encoder refuses")
+    return buf.raw[:n]
+
+
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     """Loads the HIP library.  torch (if installed) is imported first so the
     process ends up with one HIP runtime (torch ships its own
@@ -511,6 +534,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         if hasattr(lib, name):  # (absent from builds before the frame ingest loaded through HL_LIB)
             getattr(lib, name).argtypes = args
             getattr(lib, name).restype = i32
+    for name, args in (("hl_amd_set_au_display_size", [vp, i32, i32]),
+                       ("hl_amd_get_au_display_size", [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+                       ("hl_amd_encode_au_frame", [vp, pf, ctypes.POINTER(_Result)]),
+                       ("hl_amd_encode_au_frames", [vp, i32, pf, ctypes.POINTER(_Result)])):
+        if hasattr(lib, name):  # (absent from builds before the access unit's display size loaded through HL_LIB)
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = i32
+    if hasattr(lib, "hl_amd_svc_stream_headers"):
+        lib.hl_amd_svc_stream_headers.argtypes = [ctypes.POINTER(_Params), i32, i32, i32, i32, vp, ctypes.c_size_t]
+        lib.hl_amd_svc_stream_headers.restype = ctypes.c_size_t
     lib.hl_amd_svc_layer_ms.argtypes = [vp]
     lib.hl_amd_svc_layer_ms.restype = ctypes.c_float
     lib.hl_amd_version.argtypes = []
@@ -1135,6 +1168,60 @@ class SvcEncoder(Encoder):
         if rc != HL_AMD_SUCCESS:
             raise HlAmdError(rc, "hl_amd_get_layer_input")
         return out
+
+    def set_au_display_size(self, width: int, height: int) -> None:
+        """The size a decoder shows of the top layer (hl_amd_set_au_display_size):
+        multiples of 2 << K within 16 << K of the top coded size (K = layers -
+        1); layer l shows it shifted right by K - l.  SPS 0 and every subset
+        SPS then carry the cropping offsets, encode_au_frame and
+        encode_au_frames_device take frames of this size and pad them on the
+        GPU, and quality covers each layer's display rectangle; every other
+        encode call keeps taking planes of the coded sizes.  Before the first
+        picture."""
+        rc = self.lib.hl_amd_set_au_display_size(self._h, width, height)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_set_au_display_size")
+
+    @property
+    def au_display_size(self):
+        """(width, height) a decoder shows of the top layer: its coded size unless set_au_display_size set another."""
+        w, h = ctypes.c_int32(), ctypes.c_int32()
+        rc = self.lib.hl_amd_get_au_display_size(self._h, ctypes.byref(w), ctypes.byref(h))
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_get_au_display_size")
+        return w.value, h.value
+
+    def _check_frame(self, f: "Frame"):
+        """a frame of a known size has the top layer's display size (its coded size unless one was set)"""
+        if f.width and (f.width, f.height) != self.au_display_size:
+            raise HlAmdError(HL_AMD_ERROR_INVALID_FORMAT, "frame (picture size)")
+
+    def encode_au_frame(self, frame: "Frame") -> EncodeResult:
+        """One access unit from one frame by its description -- any format, on
+        the host or in device memory, of the top display size -- converted and
+        padded on the GPU and coded as encode_au codes the padded top planes
+        (hl_amd_encode_au_frame)."""
+        self._check_frame(frame)
+        r = _Result()
+        c = frame._c()
+        rc = self.lib.hl_amd_encode_au_frame(self._h, ctypes.byref(c), ctypes.byref(r))
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_au_frame")
+        return self._result(r)
+
+    def encode_au_frames_device(self, frames):
+        """n access units from n frames in device memory by their descriptions,
+        converted on the GPU (one launch per format) and coded as
+        encode_aus_batch_device codes frames (hl_amd_encode_au_frames)."""
+        n = len(frames)
+        for f in frames:
+            self._check_frame(f)
+        arr = (_Frame * n)(*[f._c() for f in frames])
+        res = (_Result * n)()
+        rc = self.lib.hl_amd_encode_au_frames(self._h, n, arr, res)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_au_frames")
+        return [self._result(r) for r in res]
 
     def bench_pyramid(self, iters: int = 50) -> float:
         """average ms per launch of k_pyramid on the last encode_au's frame (diagnostics)"""

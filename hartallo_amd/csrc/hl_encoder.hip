@@ -1240,6 +1240,7 @@ struct hl_amd_encoder_s {
         int fmt, frames;
     };
     std::vector<InLaunch> in_launches;           // the last frame call's launches (hl_amd_bench_ingest)
+    int in_max_margin = 16;                      // ... and their launch_ingest max_margin (16 << K for access-unit frames)
     std::vector<const uint8_t*> in_src;          // [3 k + c] the converted planes of its picture k, null: forwarded
     bool in_ok = false;                          // the last encode call was a frame call and ended well
     bool in_nested = false;                      // inside a frame call (encode_pictures keeps the above)
@@ -1250,6 +1251,7 @@ static hipError_t svc_drain_el(hl_amd_encoder_t* e);
 static bool svc_started(const hl_amd_encoder_t* e);
 static int svc_layer_count(const hl_amd_encoder_t* e);                      // 1 without layers
 static void svc_layer_size(const hl_amd_encoder_t* e, int l, int& W, int& H);
+static bool svc_display(const hl_amd_encoder_t* e, int l, int& dw, int& dh);  // layer l's display size; false: none was set
 
 static void free_all(hl_amd_encoder_t* e)
 {
@@ -2888,6 +2890,7 @@ extern "C" int32_t hl_amd_last_quality(hl_amd_encoder_t* e, int32_t layer, int32
         W = e->dW;
         H = e->dH;
     }
+    else (void)svc_display(e, layer, W, H);  // hl_amd_set_au_display_size: the layer's display rectangle
     const unsigned long long* s = e->h_q_sums + (size_t)6 * ((size_t)layer * e->q_cap + k);
     for (int c = 0; c < 3; ++c) {
         const int w = c ? W >> 1 : W, h = c ? H >> 1 : H;
@@ -3045,12 +3048,12 @@ static int32_t check_frames(const hl_amd_encoder_t* e, const hl_amd_frame_t* f, 
 }
 
 // a (checked) device frame as k_ingest takes it; dst stays to be set
-static InFrame in_describe(const hl_amd_encoder_t* e, const hl_amd_frame_t& f)
+static InFrame in_describe(const hl_amd_frame_t& f, int dW)
 {
     InFrame F{};
     for (int c = 0; c < in_planes(f.format); ++c) {
         F.plane[c] = f.plane[c];
-        F.pitch[c] = f.pitch[c] ? f.pitch[c] : in_row_bytes(f.format, c, e->dW);
+        F.pitch[c] = f.pitch[c] ? f.pitch[c] : in_row_bytes(f.format, c, dW);
     }
     return F;
 }
@@ -3059,12 +3062,12 @@ static InFrame in_describe(const hl_amd_encoder_t* e, const hl_amd_frame_t& f)
 // bytes rounded up to a multiple of 4 as the pitch (k_ingest's word loads; the
 // coded size's rows are such multiples, a display width like 34 is not):
 // padding is not read
-static int32_t in_stage(hl_amd_encoder_t* e, const hl_amd_frame_t& f, InFrame* S)
+static int32_t in_stage(hl_amd_encoder_t* e, const hl_amd_frame_t& f, int dW, int dH, InFrame* S)
 {
     size_t at[3] = {}, total = 0;
     for (int c = 0; c < in_planes(f.format); ++c) {
         at[c] = total;
-        total += ((((size_t)in_row_bytes(f.format, c, e->dW) + 3) & ~(size_t)3) * in_rows(f.format, c, e->dH) + 255) & ~(size_t)255;
+        total += ((((size_t)in_row_bytes(f.format, c, dW) + 3) & ~(size_t)3) * in_rows(f.format, c, dH) + 255) & ~(size_t)255;
     }
     if (e->stage_cap < total) {
         (void)hipFree(e->d_stage);
@@ -3074,7 +3077,7 @@ static int32_t in_stage(hl_amd_encoder_t* e, const hl_amd_frame_t& f, InFrame* S
         e->stage_cap = total;
     }
     for (int c = 0; c < in_planes(f.format); ++c) {
-        const size_t rb = (size_t)in_row_bytes(f.format, c, e->dW), rows = (size_t)in_rows(f.format, c, e->dH), sp = (rb + 3) & ~(size_t)3;
+        const size_t rb = (size_t)in_row_bytes(f.format, c, dW), rows = (size_t)in_rows(f.format, c, dH), sp = (rb + 3) & ~(size_t)3;
         const size_t pitch = f.pitch[c] ? (size_t)f.pitch[c] : rb;
         if (pitch == rb && sp == rb) HL_HIP_CHECK(hipMemcpyAsync(e->d_stage + at[c], f.plane[c], rb * rows, hipMemcpyHostToDevice, e->stream));
         else HL_HIP_CHECK(hipMemcpy2DAsync(e->d_stage + at[c], sp, f.plane[c], pitch, rb, rows, hipMemcpyHostToDevice, e->stream));
@@ -3088,9 +3091,9 @@ static int32_t in_stage(hl_amd_encoder_t* e, const hl_amd_frame_t& f, InFrame* S
 static int32_t in_one(hl_amd_encoder_t* e, const hl_amd_frame_t& f, uint8_t* const* dst)
 {
     InArgs A{};
-    if (f.on_device) A.one = in_describe(e, f);
+    if (f.on_device) A.one = in_describe(f, e->dW);
     else {
-        const int32_t rc = in_stage(e, f, &A.one);
+        const int32_t rc = in_stage(e, f, e->dW, e->dH, &A.one);
         if (rc) return rc;
     }
     for (int c = 0; c < 3; ++c) A.one.dst[c] = dst[c];
@@ -3127,6 +3130,7 @@ extern "C" int32_t hl_amd_encode_frame(hl_amd_encoder_t* e, const hl_amd_frame_t
     const bool fwd = in_forwarded(e, *f);
     const size_t ny = (size_t)e->W * e->H, nc = (size_t)e->Wc * e->Hc, fb = ny + 2 * nc;
     e->in_launches.clear();
+    e->in_max_margin = 16;
     e->in_src.assign(3, nullptr);
     if (e->lookahead > 1) {  // as hl_amd_encode_ex: the frame goes into the queue's next slot, a full queue is coded
         if (!e->d_la) HL_HIP_CHECK(hipMalloc(&e->d_la, fb * e->lookahead));
@@ -3199,6 +3203,7 @@ extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl
     }
     // the table, format by format (one launch per format); frame i keeps its place in the call
     e->in_launches.clear();
+    e->in_max_margin = 16;
     e->in_src.assign((size_t)3 * n, nullptr);
     e->in_tab.clear();
     std::vector<const uint8_t*> y(n), u(n), v(n);
@@ -3207,7 +3212,7 @@ extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl
         first[fmt] = e->in_tab.size();
         for (int i = 0; i < n; ++i) {
             if (f[i].format != fmt || in_forwarded(e, f[i])) continue;
-            InFrame F = in_describe(e, f[i]);
+            InFrame F = in_describe(f[i], e->dW);
             uint8_t* d = e->d_inb + fb * e->in_tab.size();
             y[i] = e->in_src[3 * (size_t)i] = F.dst[0] = d;
             u[i] = e->in_src[3 * (size_t)i + 1] = F.dst[1] = d + ny;
@@ -3246,7 +3251,7 @@ extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl
 extern "C" int32_t hl_amd_get_input(hl_amd_encoder_t* e, int32_t k, uint8_t* y, uint8_t* u, uint8_t* v)
 {
     if (!e || !y || !u || !v || k < 0) return HL_AMD_ERROR_INVALID_PARAMETER;
-    if (!e->in_ok || e->lookahead > 1) return HL_AMD_ERROR_INVALID_STATE;
+    if (!e->in_ok || e->lookahead > 1 || e->svc) return HL_AMD_ERROR_INVALID_STATE;  // (layers: hl_amd_get_layer_input shows the planes)
     if ((size_t)3 * k + 2 >= e->in_src.size()) return HL_AMD_ERROR_INVALID_PARAMETER;
     const uint8_t* const* p = &e->in_src[(size_t)3 * k];
     if (!p[0]) return HL_AMD_ERROR_INVALID_STATE;  // forwarded: the planes are the caller's
@@ -3267,10 +3272,10 @@ extern "C" int32_t hl_amd_bench_ingest(hl_amd_encoder_t* e, int32_t iters, float
     hipEvent_t a, b;
     HL_HIP_CHECK(hipEventCreate(&a));
     HL_HIP_CHECK(hipEventCreate(&b));
-    for (const auto& L : e->in_launches) HL_HIP_CHECK(launch_ingest(L.A, L.fmt, L.frames, e->stream));  // warm
+    for (const auto& L : e->in_launches) HL_HIP_CHECK(launch_ingest(L.A, L.fmt, L.frames, e->stream, e->in_max_margin));  // warm
     HL_HIP_CHECK(hipEventRecord(a, e->stream));
     for (int i = 0; i < iters; ++i)
-        for (const auto& L : e->in_launches) HL_HIP_CHECK(launch_ingest(L.A, L.fmt, L.frames, e->stream));
+        for (const auto& L : e->in_launches) HL_HIP_CHECK(launch_ingest(L.A, L.fmt, L.frames, e->stream, e->in_max_margin));
     HL_HIP_CHECK(hipEventRecord(b, e->stream));
     HL_HIP_CHECK(hipEventSynchronize(b));
     float t = 0.f;
@@ -3514,6 +3519,11 @@ struct SvcState {
     const uint8_t** d_pyr_tab = nullptr;         // batch: the top planes' table on the device [3 * frames]
     size_t pyr_tab_cap = 0;
     std::vector<const uint8_t*> pyr_planes;      // batch: the plane table handed to hl_amd_encode_layers_batch
+    // hl_amd_set_au_display_size: the display size of every layer (the top
+    // layer's shifted down), empty: none -- headers, quality windows and the
+    // size of the frames hl_amd_encode_au_frame(s) take
+    std::vector<int32_t> dws, dhs;
+    std::vector<const uint8_t*> auf_planes;      // hl_amd_encode_au_frames: the converted top planes' table
 };
 
 static bool svc_started(const hl_amd_encoder_t* e) { return e->svc && e->svc->started; }
@@ -3522,6 +3532,24 @@ static void svc_layer_size(const hl_amd_encoder_t* e, int l, int& W, int& H)
 {
     W = l ? e->svc->w[l] : e->W;
     H = l ? e->svc->h[l] : e->H;
+}
+static bool svc_display(const hl_amd_encoder_t* e, int l, int& dw, int& dh)
+{
+    const SvcState* s = e->svc;
+    if (!s || l < 0 || l >= (int)s->dws.size()) return false;
+    dw = s->dws[l];
+    dh = s->dhs[l];
+    return true;
+}
+// the header NAL units once layers [0, n) exist (write_svc_headers with the encoder's settings)
+static void svc_headers(const hl_amd_encoder_t* e, int n, std::vector<uint8_t>& out)
+{
+    const SvcState* s = e->svc;
+    const StreamParams bp{s->w[0], s->h[0], e->p.qp, e->p.deblock, e->max_ref_frame};
+    const bool disp = !s->dws.empty();
+    out.resize(1024);
+    out.resize(write_svc_headers(bp, s->w.data(), s->h.data(), n, out.data(), out.size(), disp ? s->dws.data() : nullptr,
+                                 disp ? s->dhs.data() : nullptr));
 }
 
 static void svc_free(hl_amd_encoder_t* e)
@@ -3732,6 +3760,7 @@ static int32_t svc_encode_el(hl_amd_encoder_t* e, int l, const uint8_t* y, const
         Q.mb = e->d_q_mb[l] + (size_t)L.nmb * s->q_k;
         Q.W = L.W;
         Q.H = L.H;
+        (void)svc_display(e, l, Q.dW, Q.dH);  // hl_amd_set_au_display_size: the layer's display rectangle only (else 0, 0: the picture)
         HL_HIP_CHECK(hipMemsetAsync(Q.sums, 0, sizeof(unsigned long long) * 6, st));
         HL_HIP_CHECK(hl::launch_quality(Q, 1, st));
         HL_HIP_CHECK(hipMemcpyAsync(e->h_q_sums + 6 * slot, Q.sums, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, st));
@@ -3836,9 +3865,72 @@ extern "C" int32_t hl_amd_set_layer_range(hl_amd_encoder_t* e, int32_t first, in
     SvcState* s = e->svc;
     if (s->started) return HL_AMD_ERROR_INVALID_STATE;
     if (first < 0 || last < first || last >= (int)s->w.size()) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!s->dws.empty() && (first != 0 || last != (int)s->w.size() - 1)) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // (a display size: all layers here)
     s->first = first;
     s->last = last;
     return HL_AMD_SUCCESS;
+}
+
+// The access unit's display size: that of the top layer; layer l's is it
+// shifted right by K - l (no reference interface, like
+// hl_amd_set_display_size).  Part of the SPS and of every subset SPS, so it is
+// taken once the layers exist and before the first picture.  The base layer's
+// goes through the encoder's own display size (its SPS, its quality window).
+extern "C" int32_t hl_amd_set_au_display_size(hl_amd_encoder_t* e, int32_t width, int32_t height)
+{
+    if (!e) return HL_AMD_ERROR_INVALID_PARAMETER;
+    SvcState* s = e->svc;
+    if (!s || s->w.size() < 2) return HL_AMD_ERROR_INVALID_STATE;  // no layers (yet)
+    const int layers = (int)s->w.size(), K = layers - 1, W = s->w[K], H = s->h[K];
+    if (!svc_display_size_ok(layers, W, H, width, height)) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->frame_index != 0 || s->started) return HL_AMD_ERROR_INVALID_STATE;  // the headers are out, or an access unit is under way
+    const bool none = width == W && height == H;
+    if (!none && (s->first != 0 || s->last != K)) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // hl_amd_set_layer_range
+    s->dws.clear();
+    s->dhs.clear();
+    for (int l = 0; l < layers && !none; ++l) {
+        s->dws.push_back(width >> (K - l));
+        s->dhs.push_back(height >> (K - l));
+    }
+    e->dW = width >> K;
+    e->dH = height >> K;
+    rebuild_headers(e);
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_get_au_display_size(hl_amd_encoder_t* e, int32_t* width, int32_t* height)
+{
+    if (!e || !width || !height) return HL_AMD_ERROR_INVALID_PARAMETER;
+    const SvcState* s = e->svc;
+    if (!s || s->w.size() < 2) return HL_AMD_ERROR_INVALID_STATE;
+    *width = s->dws.empty() ? s->w.back() : s->dws.back();
+    *height = s->dhs.empty() ? s->h.back() : s->dhs.back();
+    return HL_AMD_SUCCESS;
+}
+
+// every header NAL unit of an encoder with these settings and layers (a pure function; no device)
+extern "C" size_t hl_amd_svc_stream_headers(const hl_amd_params_t* p, int32_t max_ref_frame, int32_t layers, int32_t display_width,
+                                            int32_t display_height, uint8_t* out, size_t cap)
+{
+    if (!p || !out || p->width <= 0 || p->height <= 0 || (p->width & 15) || (p->height & 15) || p->qp < 0 || p->qp > 51) return 0;
+    if (layers < 2 || layers > 4 || p->width > (1 << 14) || p->height > (1 << 14)) return 0;
+    if (max_ref_frame < 0 || sps_max_num_ref_frames(p->width, p->height, max_ref_frame) > 16) return 0;
+    const int K = layers - 1, W = p->width << K, H = p->height << K;
+    if (!svc_display_size_ok(layers, W, H, display_width, display_height)) return 0;
+    int32_t w[4], h[4], dw[4], dh[4];
+    for (int l = 0; l < layers; ++l) {
+        w[l] = p->width << l;
+        h[l] = p->height << l;
+        dw[l] = display_width >> (K - l);
+        dh[l] = display_height >> (K - l);
+    }
+    const bool none = display_width == W && display_height == H;
+    const StreamParams bp{p->width, p->height, p->qp, p->deblock, max_ref_frame};
+    uint8_t buf[1024];
+    const size_t n = write_svc_headers(bp, w, h, layers, buf, sizeof(buf), none ? nullptr : dw, none ? nullptr : dh);
+    if (!n || n > cap) return 0;
+    memcpy(out, buf, n);
+    return n;
 }
 
 static int32_t svc_start(hl_amd_encoder_t* e)
@@ -3858,6 +3950,7 @@ extern "C" int32_t hl_amd_encode_layer(hl_amd_encoder_t* e, int32_t width, int32
                                        const uint8_t* v, int32_t on_device, hl_amd_result_t* r)
 {
     if (!e || !y || !u || !v || !r) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->in_nested) e->in_ok = false;  // not a frame call: hl_amd_bench_ingest has nothing to repeat
     SvcState* s = e->svc;
     if (!s || s->w.size() < 2) {
         if (width != e->W || height != e->H) return HL_AMD_ERROR_INVALID_FORMAT;
@@ -3915,9 +4008,7 @@ extern "C" int32_t hl_amd_encode_layer(hl_amd_encoder_t* e, int32_t width, int32
         rc = svc_encode_el(e, l, y, u, v);
         if (rc != HL_AMD_SUCCESS) return rc;
         if (l >= s->hdr_layers) {  // hl_codec_264.c:577-687: a new (subset) SPS and PPS
-            s->hdr.resize(1024);
-            const StreamParams bp{s->w[0], s->h[0], e->p.qp, e->p.deblock, e->max_ref_frame};
-            s->hdr.resize(write_svc_headers(bp, s->w.data(), s->h.data(), l + 1, s->hdr.data(), s->hdr.size()));
+            svc_headers(e, l + 1, s->hdr);
             s->hdr_layers = l + 1;
             r->type |= HL_AMD_RESULT_TYPE_HDR;
         }
@@ -4074,6 +4165,7 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
                                               hl_amd_result_t* results)
 {
     if (!e || n <= 0 || !planes || !results) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->in_nested) e->in_ok = false;  // not a frame call
     SvcState* s = e->svc;
     if (!s || (int)s->w.size() != layers || layers < 2) return HL_AMD_ERROR_INVALID_STATE;
     for (int i = 0; i < 3 * n * layers; ++i)
@@ -4201,9 +4293,8 @@ extern "C" int32_t hl_amd_encode_layers_batch(hl_amd_encoder_t* e, int32_t n, in
                 const uint8_t* const* p = planes + ((size_t)l * n + i) * 3;
                 r = svc_encode_el(e, l, p[0], p[1], p[2]);
                 if (r == HL_AMD_SUCCESS && l >= s->hdr_layers) {  // hl_codec_264.c:577-687: a new (subset) SPS and PPS
-                    std::vector<uint8_t> h(1024);
-                    const StreamParams bp0{s->w[0], s->h[0], e->p.qp, e->p.deblock, e->max_ref_frame};
-                    h.resize(write_svc_headers(bp0, s->w.data(), s->h.data(), l + 1, h.data(), h.size()));
+                    std::vector<uint8_t> h;
+                    svc_headers(e, l + 1, h);
                     hdr.insert(hdr.end(), h.begin(), h.end());
                     s->hdr_layers = l + 1;
                 }
@@ -4442,6 +4533,172 @@ extern "C" int32_t hl_amd_encode_aus_batch(hl_amd_encoder_t* e, int32_t n, const
         }
     // (the batch orders its two streams after what is queued on the encoder's stream: the pyramid)
     return hl_amd_encode_layers_batch(e, n, layers, s->pyr_planes.data(), results);
+}
+
+// ---------------------------------------------------------------------------
+// Access units from described frames (no reference interface):
+// hl_amd_encode_frame / hl_amd_encode_frames for an encoder with layers.  The
+// frame has the top layer's display size (hl_amd_set_au_display_size; the top
+// coded size without one); k_ingest and k_ingest_edge (hl_ingest.h) write the
+// top layer's dense coded planes on the encoder's stream -- margins up to
+// (16 << K) - 2 -- and hl_amd_encode_au / hl_amd_encode_aus_batch code the
+// access units from them: k_pyramid, the layers and every rule are theirs.
+// ---------------------------------------------------------------------------
+// the top layer's coded size and the size of the frames
+static void auf_sizes(const SvcState* s, int& W, int& H, int& dW, int& dH)
+{
+    W = dW = s->w.back();
+    H = dH = s->h.back();
+    if (!s->dws.empty()) {
+        dW = s->dws.back();
+        dH = s->dhs.back();
+    }
+}
+
+// a dense I420 device frame of the coded size: hl_amd_encode_au's frame as it is
+static bool auf_forwarded(const SvcState* s, const hl_amd_frame_t& f)
+{
+    int W, H, dW, dH;
+    auf_sizes(s, W, H, dW, dH);
+    if (!f.on_device || f.format != HL_AMD_FORMAT_I420 || dW != W || dH != H) return false;
+    for (int c = 0; c < 3; ++c)
+        if (f.pitch[c] && f.pitch[c] != in_row_bytes(IN_I420, c, W)) return false;
+    return true;
+}
+
+// every frame of a call, before anything is uploaded or launched (check_frames' rules; forward: hl_amd_encode_au_frame)
+static int32_t auf_check(const SvcState* s, const hl_amd_frame_t* f, int n, bool device_only, bool forward)
+{
+    int W, H, dW, dH;
+    auf_sizes(s, W, H, dW, dH);
+    for (int i = 0; i < n; ++i) {
+        if (f[i].format < 0 || f[i].format >= IN_FORMATS) return HL_AMD_ERROR_INVALID_PARAMETER;
+        if (device_only && !f[i].on_device) return HL_AMD_ERROR_INVALID_PARAMETER;
+        for (int c = 0; c < in_planes(f[i].format); ++c)
+            if (!f[i].plane[c] || f[i].pitch[c] < 0 || (f[i].pitch[c] && f[i].pitch[c] < in_row_bytes(f[i].format, c, dW)))
+                return HL_AMD_ERROR_INVALID_PARAMETER;
+        if (forward && auf_forwarded(s, f[i])) continue;  // (hl_amd_encode_au copies planes its 8-byte loads cannot take)
+        if (f[i].on_device)                               // k_ingest loads 4-byte words
+            for (int c = 0; c < in_planes(f[i].format); ++c) {
+                const uint64_t pitch = f[i].pitch[c] ? (uint64_t)f[i].pitch[c] : (uint64_t)in_row_bytes(f[i].format, c, dW);
+                if (((uintptr_t)f[i].plane[c] | pitch) & 3) return HL_AMD_ERROR_INVALID_PARAMETER;
+            }
+    }
+    return HL_AMD_SUCCESS;
+}
+
+// the refusals both calls share, before any frame is looked at
+static int32_t auf_state(const hl_amd_encoder_t* e)
+{
+    const SvcState* s = e->svc;
+    if (!s || s->w.size() < 2) return HL_AMD_ERROR_INVALID_STATE;
+    if (e->broken) return HL_AMD_ERROR_INVALID_STATE;  // an earlier GPU failure
+    if (s->first != 0 || s->last != (int)s->w.size() - 1) return HL_AMD_ERROR_INVALID_STATE;  // every layer is derived and coded here
+    if (s->started && s->next != s->first) return HL_AMD_ERROR_INVALID_STATE;                // inside an access unit of layer calls
+    if (e->rc) return HL_AMD_ERROR_NOT_IMPLEMENTED;                                           // as the layer calls (svc_start)
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_encode_au_frame(hl_amd_encoder_t* e, const hl_amd_frame_t* f, hl_amd_result_t* r)
+{
+    if (!e || !f || !r) return HL_AMD_ERROR_INVALID_PARAMETER;
+    int32_t rc = auf_state(e);
+    if (rc) return rc;
+    SvcState* s = e->svc;
+    rc = auf_check(s, f, 1, false, true);
+    if (rc) return rc;  // (a refused call leaves everything as it was, hl_amd_bench_ingest's launches included)
+    e->in_ok = false;
+    if (auf_forwarded(s, *f)) return hl_amd_encode_au(e, f->plane[0], f->plane[1], f->plane[2], 1, r);
+    const int layers = (int)s->w.size();
+    InArgs A{};
+    auf_sizes(s, A.W, A.H, A.dW, A.dH);
+    if (f->on_device) A.one = in_describe(*f, A.dW);
+    else if ((rc = in_stage(e, *f, A.dW, A.dH, &A.one))) return rc;  // (before svc_start: a failed upload does not start the stream)
+    rc = svc_start(e);
+    if (rc != HL_AMD_SUCCESS) return rc;
+    SvcLayerDev& T = s->el[layers - 2];
+    for (int c = 0; c < 3; ++c) A.one.dst[c] = T.d_in[c];
+    A.coef = in_coef_of(e->in_matrix, e->in_range);
+    e->in_launches.clear();
+    e->in_src.clear();  // (hl_amd_get_layer_input shows the planes)
+    e->in_max_margin = 16 << (layers - 1);
+    HL_HIP_CHECK(launch_ingest(A, f->format, 1, e->stream, e->in_max_margin));
+    e->in_launches.push_back({A, f->format, 1});
+    e->in_nested = true;
+    rc = hl_amd_encode_au(e, T.d_in[0], T.d_in[1], T.d_in[2], 1, r);
+    e->in_nested = false;
+    e->in_ok = rc == HL_AMD_SUCCESS;
+    return rc;
+}
+
+extern "C" int32_t hl_amd_encode_au_frames(hl_amd_encoder_t* e, int32_t n, const hl_amd_frame_t* f, hl_amd_result_t* results)
+{
+    if (!e || n <= 0 || !f || !results) return HL_AMD_ERROR_INVALID_PARAMETER;
+    int32_t rc = auf_state(e);
+    if (rc) return rc;
+    SvcState* s = e->svc;
+    rc = auf_check(s, f, n, true, false);
+    if (rc) return rc;  // (a refused call leaves everything as it was)
+    e->in_ok = false;
+    rc = svc_start(e);
+    if (rc != HL_AMD_SUCCESS) return rc;
+    int W, H, dW, dH;
+    auf_sizes(s, W, H, dW, dH);
+    const int layers = (int)s->w.size();
+    const size_t ny = (size_t)W * H, nc = ny / 4, fb = ny + 2 * nc;  // (multiples of 64: every plane of the buffer is 8-byte aligned)
+    if (e->inb_cap < fb * n) {
+        (void)hipFree(e->d_inb);
+        e->d_inb = nullptr;
+        e->inb_cap = 0;
+        if (hipMalloc(&e->d_inb, fb * n) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e->inb_cap = fb * n;
+    }
+    if (e->in_tab_cap < (size_t)n) {
+        (void)hipFree(e->d_in_tab);
+        e->d_in_tab = nullptr;
+        e->in_tab_cap = 0;
+        if (hipMalloc(&e->d_in_tab, sizeof(InFrame) * n) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e->in_tab_cap = n;
+    }
+    // the table, format by format (one launch per format); frame i keeps its place in the call and in the buffer
+    e->in_launches.clear();
+    e->in_src.clear();
+    e->in_tab.clear();
+    e->in_max_margin = 16 << (layers - 1);
+    s->auf_planes.resize((size_t)3 * n);
+    size_t first[IN_FORMATS + 1] = {};
+    for (int fmt = 0; fmt < IN_FORMATS; ++fmt) {
+        first[fmt] = e->in_tab.size();
+        for (int i = 0; i < n; ++i) {
+            if (f[i].format != fmt) continue;
+            InFrame F = in_describe(f[i], dW);
+            uint8_t* d = e->d_inb + fb * i;
+            s->auf_planes[3 * (size_t)i] = F.dst[0] = d;
+            s->auf_planes[3 * (size_t)i + 1] = F.dst[1] = d + ny;
+            s->auf_planes[3 * (size_t)i + 2] = F.dst[2] = d + ny + nc;
+            e->in_tab.push_back(F);
+        }
+    }
+    first[IN_FORMATS] = e->in_tab.size();
+    HL_HIP_CHECK(hipMemcpyAsync(e->d_in_tab, e->in_tab.data(), sizeof(InFrame) * n, hipMemcpyHostToDevice, e->stream));
+    for (int fmt = 0; fmt < IN_FORMATS; ++fmt)
+        for (size_t f0 = first[fmt]; f0 < first[fmt + 1]; f0 += 65535) {  // grid z holds the frames
+            InArgs A{};
+            A.tab = e->d_in_tab + f0;
+            A.coef = in_coef_of(e->in_matrix, e->in_range);
+            A.W = W;
+            A.H = H;
+            A.dW = dW;
+            A.dH = dH;
+            const int frames = (int)std::min<size_t>(65535, first[fmt + 1] - f0);
+            HL_HIP_CHECK(launch_ingest(A, fmt, frames, e->stream, e->in_max_margin));
+            e->in_launches.push_back({A, fmt, frames});
+        }
+    e->in_nested = true;
+    rc = hl_amd_encode_aus_batch(e, n, s->auf_planes.data(), results);  // (it waits for the stream: in_tab may go)
+    e->in_nested = false;
+    e->in_ok = rc == HL_AMD_SUCCESS;
+    return rc;
 }
 
 extern "C" int32_t hl_amd_get_layer_input(hl_amd_encoder_t* e, int32_t layer, uint8_t* y, uint8_t* u, uint8_t* v)

@@ -242,7 +242,9 @@ inline void in_frame(const InFrame& F, const InCoef& C, int W, int H)
 // source 2x2 block (min(bx, dW / 2 - 1), min(by, dH / 2 - 1)) -- for RGB that
 // block's SR, SG, SB through the arithmetic above.  A tile is full when
 // tx < (dW >> 4) and ty < (dH >> 1): in_tile as it is.  Every other tile of the
-// coded picture (at most one tile column and seven tile rows) is an edge tile:
+// coded picture (at most one tile column and seven tile rows; with spatial
+// layers, hl_amd_set_au_display_size, the top layer's margins go up to
+// (16 << K) - 2: several tile columns, up to 63 tile rows) is an edge tile:
 // in_tile_edge, which loads single bytes by clamped coordinate -- a 4-byte
 // word could cross the end of a row whose bytes are no multiple of 4 -- and
 // stores what in_tile stores.
@@ -250,7 +252,9 @@ inline void in_frame(const InFrame& F, const InCoef& C, int W, int H)
 // tiles of a row pair and row pairs that are full
 constexpr int in_full_x(int dW) { return dW >> 4; }
 constexpr int in_full_y(int dH) { return dH >> 1; }
-// edge tiles of a picture: the right column's, then the bottom rows' left of it
+// edge tiles of a picture: the right band's (the tile columns right of the full
+// ones: one within a macroblock's margin, up to eight for a top layer), then the
+// bottom rows' left of it
 constexpr int in_edge_tiles(int W, int H, int dW, int dH)
 {
     return ((W >> 4) - in_full_x(dW)) * (H >> 1) + in_full_x(dW) * ((H >> 1) - in_full_y(dH));
@@ -335,16 +339,17 @@ HL_IN_HD void in_tile_edge(const InFrame& F, const InCoef& C, int W, int dW, int
     in_store<2>(F.dst[2] + (size_t)ty * (W >> 1) + 8 * tx, vo);
 }
 
-// Edge tile i (< in_edge_tiles) of a picture: the right column's tiles row
-// pair by row pair, then the bottom rows' tiles left of that column
+// Edge tile i (< in_edge_tiles) of a picture: the right band's tiles row pair
+// by row pair (its ex tile columns left to right), then the bottom rows' tiles
+// left of that band
 HL_IN_HD void in_edge_at(int i, int W, int H, int dW, int dH, int* tx, int* ty)
 {
     const int fx = in_full_x(dW), ex = (W >> 4) - fx, right = ex * (H >> 1);
-    if (i < right) {  // (ex = 1)
-        *tx = fx;
-        *ty = i;
+    if (i < right) {  // (ex = 1 within a macroblock's margin: tx = fx, ty = i)
+        *tx = fx + i % ex;
+        *ty = i / ex;
     }
-    else {  // (fx > 0: there are tiles left of the column)
+    else {  // (fx > 0: there are tiles left of the band)
         const int j = i - right;
         *ty = in_full_y(dH) + j / fx;
         *tx = j - (j / fx) * fx;
@@ -378,8 +383,13 @@ struct InArgs {
 constexpr int kInEdgeLanes = 64;  // lanes of a workgroup of k_ingest_edge: one edge tile each
 
 // `frames` frames of format fmt on `stream`: k_ingest on the full tiles and,
-// for frames below the coded size, k_ingest_edge on the others
-hipError_t launch_ingest(const InArgs& A, int fmt, int frames, hipStream_t stream);
+// for frames below the coded size, k_ingest_edge on the others.  The margins
+// W - dW and H - dH must be below max_margin: 16 for the AVC path (a display
+// size lies within the last macroblock column and row), 16 << K for the top
+// layer of K + 1 spatial layers (hl_amd_set_au_display_size), whose edge tiles
+// then form a right band of up to 1 << K tile columns and a bottom band of up
+// to (8 << K) - 1 tile rows (in_edge_tiles and in_edge_at take any width).
+hipError_t launch_ingest(const InArgs& A, int fmt, int frames, hipStream_t stream, int max_margin = 16);
 
 #if defined(HL_INGEST_KERNELS)  // hl_ingest.hip: the one translation unit that holds the kernels
 template <int FMT>
@@ -409,7 +419,7 @@ __global__ __launch_bounds__(kInEdgeLanes) void k_ingest_edge(InArgs A)
     else in_tile_edge<FMT>(A.one, A.coef, A.W, A.dW, A.dH, tx, ty);
 }
 
-hipError_t launch_ingest(const InArgs& A0, int fmt, int frames, hipStream_t stream)
+hipError_t launch_ingest(const InArgs& A0, int fmt, int frames, hipStream_t stream, int max_margin)
 {
     InArgs A = A0;
     if (!A.dW && !A.dH) {
@@ -417,7 +427,8 @@ hipError_t launch_ingest(const InArgs& A0, int fmt, int frames, hipStream_t stre
         A.dH = A.H;
     }
     if (fmt < 0 || fmt >= IN_FORMATS || frames < 1 || frames > 65535 || A.W <= 0 || A.H <= 0 || (A.W & 15) || (A.H & 15) || ((A.dW | A.dH) & 1) ||
-        A.dW <= A.W - 16 || A.dW > A.W || A.dH <= A.H - 16 || A.dH > A.H || A.dW <= 0 || A.dH <= 0)
+        max_margin < 16 || max_margin > 128 || A.dW <= A.W - max_margin || A.dW > A.W || A.dH <= A.H - max_margin || A.dH > A.H || A.dW <= 0 ||
+        A.dH <= 0)
         return hipErrorInvalidValue;
     if (in_full_x(A.dW) > 0) {  // (dH >= 2: a full row pair)
         const dim3 block(kInLanesX, kInLanesY);

@@ -46,6 +46,7 @@ struct SvcGeom {
     int32_t mshX, mshY, mscX, mscY;  // G.6.1: shiftX/Y, scaleX/Y (G-7..G-10)
     int32_t shX[2], shY[2], scX[2], scY[2], addX[2], addY[2], dX[2], dY[2];  // G.6.3 [chromaFlag] (G-43..G-55)
     int32_t mvsX, mvsY;          // G-232, G-233
+    int32_t rsa_bytes;           // 4096 for a layer of 4 x 4 macroblocks: the reference's refSampleArray allocation (svc_ref_array_sample); else 0
 };
 
 // shiftX/shiftY of G-7/G-43: the reference evaluates Ceil(Log2(refW)) in
@@ -89,6 +90,19 @@ inline SvcGeom svc_geom(int W, int H, int rW, int rH, int level_idc)
     }
     g.mvsX = ((W << 16) + (rW >> 1)) / rW;
     g.mvsY = ((H << 16) + (rH >> 1)) / rH;
+    // The reference allocates PicSizeInMbs << 8 BYTES for the int32 luma array
+    // of G.8.6.2.2 (layer.c:202), which a dyadic layer uses as 48 x 48 ints
+    // (G-270..G-273): 9 216 bytes.  A rewritten element is read back only up
+    // to array row 33, so the overflow shows only where the array that
+    // follows it on the heap overlaps those rows (svc_ref_array_sample).  That
+    // is modelled for exactly one geometry, the one compared with the
+    // reference: a layer of 4 x 4 macroblocks (64 x 64 over a 32 x 32 base,
+    // 4 096 bytes), luma only.  From 20 macroblocks on the overlap lies beyond
+    // row 33 and nothing shows; smaller layers and 128 x 32 / 32 x 128 have a
+    // base the reference did not code where tried (it aborts on bases of 32 x 16
+    // and 16 x 32) and would overflow other arrays too; they keep the plain
+    // G.8.6.2 code and are outside what is pinned.
+    g.rsa_bytes = g.mbw == 4 && g.mbh == 4 ? 4096 : 0;
     return g;
 }
 
@@ -267,6 +281,28 @@ HD int svc_yref16(const SvcGeom& g, int c, int mby, int yP)
 // reference-layer MB intra, so every array sample is available): the
 // separable 4-tap (luma) / 2-tap (chroma) interpolation over the reference
 // layer's picture with clamped coordinates (G-280, G-281).
+//
+// A reference quirk that is reproduced (g.rsa_bytes != 0: a layer of 4 x 4
+// macroblocks, 64 x 64, and no other): the luma array of G.8.6.2.2 is
+// 48 x 48 int32 in an allocation of rsa_bytes bytes, and the availability array (one byte per
+// element, 1 = available, written right after its element, layer.c:203-206,
+// decode_svc.c:3037-3055) is the next heap block, rsa_bytes + 16 bytes on
+// (glibc's chunk of a malloc of a multiple of 16).  Byte k of element i
+// therefore lies at availability index j = 4 i + k - (rsa_bytes + 16) and
+// holds that flag when it was written later (i <= j < 48 * 48): elements
+// 1371..1603 (array rows 28..33, the lower rows of a macroblock in an even
+// macroblock row) read 0x01010101 and element 1370 has its upper half
+// replaced.  The interpolation then runs in the reference's wrapping 32-bit
+// arithmetic.
+HD uint32_t svc_ref_array_sample(uint32_t v, int i, int rsa_bytes)
+{
+    for (int k = 0; k < 4; ++k) {
+        const int j = 4 * i + k - (rsa_bytes + 16);
+        if (j >= i && j < 48 * 48) v = (v & ~(0xFFu << (8 * k))) | (1u << (8 * k));
+    }
+    return v;
+}
+
 HD int svc_resample(const SvcGeom& g, const uint8_t* plane, int c, int mbx, int mby, int x, int y)
 {
     const int refW = c ? g.rW / 2 : g.rW, refH = c ? g.rH / 2 : g.rH;
@@ -274,7 +310,22 @@ HD int svc_resample(const SvcGeom& g, const uint8_t* plane, int c, int mbx, int 
     const int xr = xr16 >> 4, yr = yr16 >> 4, xph = xr16 & 15, yph = yr16 & 15;
     auto R = [&](int xx, int yy) -> int { return plane[clip3(0, refH - 1, yy) * refW + clip3(0, refW - 1, xx)]; };
     int v;
-    if (c == 0) {
+    if (c == 0 && g.rsa_bytes) {  // (uniform over the launch)
+        const int xOff = (((svc_xref16(g, 0, mbx, 0) - 64) >> 8) << 4) - 8, yOff = (((svc_yref16(g, 0, mby, 0) - 64) >> 8) << 4) - 8;  // G-270, G-271
+        const int arrW = (((svc_xref16(g, 0, mbx, 15) + 79) >> 8) << 4) + 24 - xOff;                                                   // G-272
+        uint32_t acc = 0;
+        for (int k = 0; k < 4; ++k) {
+            const int xx = xr - 1 + k;
+            uint32_t t = 0;
+            for (int m = 0; m < 4; ++m) {
+                const int yy = yr - 1 + m;
+                t += (uint32_t)(int32_t)kRsLuma[yph][m] * svc_ref_array_sample((uint32_t)R(xx, yy), (yy - yOff) * arrW + (xx - xOff), g.rsa_bytes);
+            }
+            acc += (uint32_t)(int32_t)kRsLuma[xph][k] * t;
+        }
+        v = (int32_t)(acc + 512u) >> 10;
+    }
+    else if (c == 0) {
         int acc = 0;
         for (int k = 0; k < 4; ++k) {
             const int xx = xr - 1 + k;

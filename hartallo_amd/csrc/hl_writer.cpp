@@ -491,8 +491,14 @@ size_t put_pps(int id, int qp, int nref, uint8_t* out, size_t cap)
 // subset_seq_parameter_set_rbsp of an enhancement layer (sps.c:535-860):
 // Scalable Baseline (83) with constraint_set0 only, the High-profile fields
 // profile 83 carries, and the SVC extension the encoder sets (sps.c:799-851)
-size_t put_subset_sps(int id, int w, int h, int nref, uint8_t* out, size_t cap)
+// With a display size dw x dh below w x h (hl_amd_set_au_display_size; 0 x 0 or
+// w x h: none) frame_cropping_flag = 1 and the four offsets follow it, in units
+// of two luma samples (they may cover whole macroblock rows and columns), and
+// the NAL unit gets emulation prevention; without one the bytes are the
+// reference's.
+size_t put_subset_sps(int id, int w, int h, int nref, int dw, int dh, uint8_t* out, size_t cap)
 {
+    const bool crop = dw > 0 && dh > 0 && (dw != w || dh != h);
     uint8_t buf[64];
     memset(buf, 0, sizeof(buf));
     BitWriter bw(buf, sizeof(buf));
@@ -517,7 +523,13 @@ size_t put_subset_sps(int id, int w, int h, int nref, uint8_t* out, size_t cap)
     bw.ue((uint32_t)(h / 16 - 1));
     bw.u1(1);       // frame_mbs_only_flag
     bw.u1(0);       // direct_8x8_inference_flag
-    bw.u1(0);       // frame_cropping_flag
+    bw.u1(crop ? 1 : 0);  // frame_cropping_flag
+    if (crop) {
+        bw.ue(0);                          // frame_crop_left_offset
+        bw.ue((uint32_t)((w - dw) / 2));   // frame_crop_right_offset (CropUnitX = 2)
+        bw.ue(0);                          // frame_crop_top_offset
+        bw.ue((uint32_t)((h - dh) / 2));   // frame_crop_bottom_offset (CropUnitY = 2)
+    }
     bw.u1(0);       // vui_parameters_present_flag
     // seq_parameter_set_svc_extension() (G.7.3.2.1.4)
     bw.u1(1);       // inter_layer_deblocking_filter_control_present_flag
@@ -529,7 +541,7 @@ size_t put_subset_sps(int id, int w, int h, int nref, uint8_t* out, size_t cap)
     bw.u1(0);       // svc_vui_parameters_present_flag
     bw.u1(0);       // additional_extension2_flag
     bw.trailing();
-    return put_nal(out, cap, buf, bw.bytes());
+    return crop ? put_nal_escaped(out, cap, buf, bw.bytes()) : put_nal(out, cap, buf, bw.bytes());
 }
 
 // TotalCoeff of the blocks the writer codes, as the reference leaves them on
@@ -554,11 +566,13 @@ int tc_cac(const MbRecord& m, int comp, int b)
 
 int stream_level_idc(int width, int height) { return guess_level(width, height); }
 
-size_t write_svc_headers(const StreamParams& base, const int32_t* widths, const int32_t* heights, int n, uint8_t* out, size_t cap)
+size_t write_svc_headers(const StreamParams& base, const int32_t* widths, const int32_t* heights, int n, uint8_t* out, size_t cap,
+                         const int32_t* dws, const int32_t* dhs)
 {
     // SPS 0 and PPS 0 are write_stream_headers' two NAL units
     uint8_t avc[256];
-    const StreamParams b0{widths[0], heights[0], base.qp, base.deblock, base.max_ref_frame};
+    const bool disp = dws && dhs;
+    const StreamParams b0{widths[0], heights[0], base.qp, base.deblock, base.max_ref_frame, disp ? dws[0] : 0, disp ? dhs[0] : 0};
     const size_t na = write_stream_headers(b0, avc, sizeof(avc));
     size_t sps0 = 3;
     while (sps0 + 2 < na && !(avc[sps0] == 0 && avc[sps0 + 1] == 0 && avc[sps0 + 2] == 1)) ++sps0;
@@ -568,7 +582,7 @@ size_t write_svc_headers(const StreamParams& base, const int32_t* widths, const 
     k = sps0;
     for (int l = 1; l < n; ++l) {
         const size_t m = put_subset_sps(l, widths[l], heights[l], sps_max_num_ref_frames(widths[l], heights[l], base.max_ref_frame),
-                                        out + k, cap - k);
+                                        disp ? dws[l] : 0, disp ? dhs[l] : 0, out + k, cap - k);
         if (!m) return 0;
         k += m;
     }

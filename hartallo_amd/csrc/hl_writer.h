@@ -107,7 +107,26 @@ size_t write_slice(const StreamParams& p, const SliceState& s, const MbRecord* r
 // level_idc the encoder writes for a picture size (utils.c:14-58)
 int stream_level_idc(int width, int height);
 
-size_t write_svc_headers(const StreamParams& base, const int32_t* widths, const int32_t* heights, int n, uint8_t* out, size_t cap);
+// dws, dhs (both or neither): the display size of every layer
+// (hl_amd_set_au_display_size) -- SPS 0 takes its cropping through
+// StreamParams::display_width / display_height, a subset SPS of a layer whose
+// display size is below its coded size carries frame_cropping_flag = 1 with
+// left 0, right (w - dw) / 2, top 0, bottom (h - dh) / 2 and is escaped like
+// the SPS; every other field, the SVC extension and the PPSs are unchanged.
+// Without them the bytes are the reference's.
+size_t write_svc_headers(const StreamParams& base, const int32_t* widths, const int32_t* heights, int n, uint8_t* out, size_t cap,
+                         const int32_t* dws = nullptr, const int32_t* dhs = nullptr);
+
+// is dw x dh a display size of the top layer of `layers` dyadic layers whose
+// top coded size is w x h: multiples of 2 << K (K = layers - 1), and within
+// 16 << K of the coded size, so that every layer's display size is even and the
+// base layer crops less than a macroblock
+inline bool svc_display_size_ok(int layers, int w, int h, int dw, int dh)
+{
+    if (layers < 2 || layers > 4) return false;
+    const int K = layers - 1, m = (2 << K) - 1, g = 16 << K;
+    return !((dw | dh) & m) && dw > w - g && dw <= w && dh > h - g && dh <= h && dw > 0 && dh > 0;
+}
 
 // Prefix NAL unit of a base-layer slice (encode.c:296-365), without start
 // code: 5 bytes.

@@ -499,6 +499,81 @@ int32_t hl_amd_encode_aus_batch(hl_amd_encoder_t* encoder, int32_t n, const uint
  * want the thumbnails, and for the tests.  No reference interface. */
 int32_t hl_amd_get_layer_input(hl_amd_encoder_t* encoder, int32_t layer, uint8_t* y, uint8_t* u, uint8_t* v);
 
+/* ---- access units of any display size, from frames in any format ----
+ * No reference interface (like hl_amd_set_display_size and
+ * hl_amd_encode_frame, whose counterparts for an encoder with layers these
+ * are).
+ *
+ * hl_amd_set_au_display_size: the display size dw x dh of the TOP layer of an
+ * encoder with L >= 2 layers (K = L - 1, top coded size W x H = the base size
+ * shifted left by K).  Accepted: dw and dh multiples of 2 << K with
+ * W - (16 << K) < dw <= W and H - (16 << K) < dh <= H, else
+ * HL_AMD_ERROR_INVALID_PARAMETER; (W, H) means none.  Layer l then has the
+ * display size (dw >> (K - l), dh >> (K - l)): even, the base layer crops less
+ * than a macroblock, layer l up to (16 << l) - 2 samples -- whole macroblock
+ * rows and columns that are coded and cropped, which H.264 allows.  1920x1080
+ * in three layers: coded 1920x1088, 960x544, 480x272; 1280x720: coded
+ * 1280x768, 640x384, 320x192.  SPS 0 carries the base layer's cropping as
+ * hl_amd_set_display_size writes it, every subset SPS frame_cropping_flag = 1
+ * with left 0, right (W_l - dw_l) / 2, top 0, bottom (H_l - dh_l) / 2 (escaped
+ * like the SPS); every other field, level_idc, max_num_ref_frames and the SVC
+ * extension included (extended_spatial_scalability_idc stays 0: inter-layer
+ * prediction is between coded sizes), the PPSs and every slice NAL unit are
+ * unchanged.  HL_AMD_ERROR_INVALID_STATE on an encoder without (all) its
+ * layers, after the first picture and inside an access unit;
+ * HL_AMD_ERROR_NOT_IMPLEMENTED together with a layer range other than all
+ * layers (hl_amd_set_layer_range, in either order).  Works in either order
+ * with hl_amd_set_max_ref_frame; hl_amd_add_layer after it returns
+ * HL_AMD_ERROR_NOT_IMPLEMENTED.  Off by default: it changes no byte of a
+ * stream coded without it.
+ * Which call takes which size: hl_amd_encode_layer, hl_amd_encode_layers_batch,
+ * hl_amd_encode_au and hl_amd_encode_aus_batch keep taking planes of the coded
+ * sizes that the caller padded (the setting changes their headers and the
+ * quality window only); hl_amd_encode_au_frame(s) take frames of the top
+ * display size.  Quality (hl_amd_last_quality, hl_amd_debug_quality_mb) then
+ * covers layer l's display rectangle. */
+int32_t hl_amd_set_au_display_size(hl_amd_encoder_t* encoder, int32_t width, int32_t height);
+/* the top layer's display size (its coded size when none was set) */
+int32_t hl_amd_get_au_display_size(hl_amd_encoder_t* encoder, int32_t* width, int32_t* height);
+
+/* Every header NAL unit ("00 00 01"-prefixed: SPS 0, the subset SPSs, the
+ * PPSs) that an encoder created with these parameters (the base layer's width
+ * and height, qp) and `layers` dyadic layers emits once every layer is coded,
+ * after hl_amd_set_max_ref_frame(max_ref_frame) and
+ * hl_amd_set_au_display_size(display_width, display_height) -- the top coded
+ * size for no cropping.  A pure function (no device), the counterpart of
+ * hl_amd_stream_headers.  Returns the bytes written, or 0 when a setting is
+ * refused or the bytes do not fit in cap. */
+size_t hl_amd_svc_stream_headers(const hl_amd_params_t* params, int32_t max_ref_frame, int32_t layers, int32_t display_width,
+                                 int32_t display_height, uint8_t* out, size_t cap);
+
+/* One access unit from one described frame (hl_amd_frame_t below), on the host
+ * or in HBM, of the top display size (the top coded size when none is set):
+ * k_ingest and, below the coded size, k_ingest_edge write the top layer's
+ * coded planes -- the edge replication of the converted frame through clamped
+ * coordinates, margins up to (16 << K) - 2; for RGB chroma still comes from the
+ * source 2x2 block -- then everything is hl_amd_encode_au's on those planes:
+ * k_pyramid derives every lower layer from the padded top picture, and the
+ * result, the GOP counter and idr_pic_id are its own.  The matrix is
+ * hl_amd_set_colour's; host frames are staged with a pitch rounded up to 4,
+ * device planes and pitches are multiples of 4.  A dense I420 device frame of
+ * the coded size is handed to hl_amd_encode_au untouched.  Every check comes
+ * before anything is uploaded or launched and a refused call leaves the
+ * encoder as it was: HL_AMD_ERROR_INVALID_STATE without layers, with a layer
+ * range, inside an access unit of layer calls and on an encoder an earlier
+ * GPU failure left unusable; HL_AMD_ERROR_NOT_IMPLEMENTED under rate control;
+ * HL_AMD_ERROR_INVALID_PARAMETER for the frame (see hl_amd_encode_frame).  No
+ * ctl: layers take no forced types. */
+struct hl_amd_frame_s;
+int32_t hl_amd_encode_au_frame(hl_amd_encoder_t* encoder, const struct hl_amd_frame_s* frame, hl_amd_result_t* result);
+
+/* n access units from n described frames in HBM (a host frame:
+ * HL_AMD_ERROR_INVALID_PARAMETER): one ingest launch per format present writes
+ * n dense top frames into a buffer the encoder owns, then
+ * hl_amd_encode_aus_batch codes them: its results, failure contract and
+ * refusals. */
+int32_t hl_amd_encode_au_frames(hl_amd_encoder_t* encoder, int32_t n, const struct hl_amd_frame_s* frames, hl_amd_result_t* results);
+
 /* Diagnostics: `iters` launches of k_pyramid on the frame of the last
  * hl_amd_encode_au (the same planes into the same buffers); *ms = average ms
  * per launch.  HL_AMD_ERROR_INVALID_STATE without such a call.  No reference
