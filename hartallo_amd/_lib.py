@@ -115,6 +115,10 @@ EXPORTED_SYMBOLS = (
     "hl_amd_encode_frames",
     "hl_amd_get_input",
     "hl_amd_bench_ingest",
+    "hl_amd_set_source_size",
+    "hl_amd_get_source_size",
+    "hl_amd_scale_taps",
+    "hl_amd_bench_scale",
     "hl_amd_set_au_display_size",
     "hl_amd_get_au_display_size",
     "hl_amd_svc_stream_headers",
@@ -375,6 +379,18 @@ def stream_headers(width: int, height: int, qp: int = 28, max_ref_frame: int = 1
     return buf.raw[:n]
 
 
+def scale_taps(s: int, d: int, j: int):
+    """(first, weights) of output sample j of the area downscaler's axis s -> d
+    (hl_amd_scale_taps; no device): the first source sample and the integer
+    weights of it and its successors, which sum to s / gcd(s, d).  ValueError
+    for what the scaler refuses: s < d, s > 8 d, s > 4096, j outside [0, d)."""
+    first, w = ctypes.c_int32(), (ctypes.c_uint32 * 9)()
+    n = load_library().hl_amd_scale_taps(s, d, j, ctypes.byref(first), w, 9)
+    if n <= 0:
+        raise ValueError("scale_taps: an axis or a sample the scaler refuses")
+    return first.value, [int(x) for x in w[:n]]
+
+
 def svc_stream_headers(width: int, height: int, layers: int, qp: int = 28, max_ref_frame: int = 1, display_width: "int | None" = None,
                        display_height: "int | None" = None) -> bytes:
     """Every header NAL unit (SPS 0, the subset SPSs, the PPSs, with start
@@ -539,6 +555,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                        ("hl_amd_encode_au_frame", [vp, pf, ctypes.POINTER(_Result)]),
                        ("hl_amd_encode_au_frames", [vp, i32, pf, ctypes.POINTER(_Result)])):
         if hasattr(lib, name):  # (absent from builds before the access unit's display size loaded through HL_LIB)
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = i32
+    for name, args in (("hl_amd_set_source_size", [vp, i32, i32]),
+                       ("hl_amd_get_source_size", [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+                       ("hl_amd_scale_taps", [i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint32), i32]),
+                       ("hl_amd_bench_scale", [vp, i32, ctypes.POINTER(ctypes.c_float)])):
+        if hasattr(lib, name):  # (absent from builds before the source size loaded through HL_LIB)
             getattr(lib, name).argtypes = args
             getattr(lib, name).restype = i32
     if hasattr(lib, "hl_amd_svc_stream_headers"):
@@ -834,9 +857,41 @@ class Encoder:
         if rc != HL_AMD_SUCCESS:
             raise HlAmdError(rc, "hl_amd_set_colour")
 
+    def set_source_size(self, width: int, height: int) -> None:
+        """The size of the frames encode_frame and encode_frames_device take
+        from now on (hl_amd_set_source_size): even, between the display size
+        and min(8 x it, 4096) on each axis.  The frames are scaled to the
+        display size on the GPU by an exact integer area filter (2:1 is the SVC
+        layers' 2x2 box) and then coded as frames of that size; the display
+        size itself turns scaling off.  Between any two calls: a source may
+        change its resolution mid-stream.  Set the display size first."""
+        rc = self.lib.hl_amd_set_source_size(self._h, width, height)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_set_source_size")
+        w, h = ctypes.c_int32(), ctypes.c_int32()
+        rc = self.lib.hl_amd_get_source_size(self._h, ctypes.byref(w), ctypes.byref(h))
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_get_source_size")
+        self._source = (w.value, h.value) if (w.value, h.value) != self.display_size else None
+
+    @property
+    def source_size(self):
+        """(width, height) of the frames the frame calls take: the display size unless set_source_size set another."""
+        return getattr(self, "_source", None) or self.display_size
+
+    def bench_scale(self, iters: int = 50) -> float:
+        """average ms of the k_scale launch(es) of the last frame call, whose
+        intermediate planes are the encoder's (diagnostics)"""
+        ms = ctypes.c_float()
+        rc = self.lib.hl_amd_bench_scale(self._h, iters, ctypes.byref(ms))
+        if rc:
+            raise HlAmdError(rc, "hl_amd_bench_scale")
+        return ms.value
+
     def _check_frame(self, f: "Frame"):
-        """a frame of a known size has the display size (the coded size unless one was set)"""
-        if f.width and (f.width, f.height) != self.display_size:
+        """a frame of a known size has the source size (the display size unless
+        one was set; the coded size unless that was set)"""
+        if f.width and (f.width, f.height) != self.source_size:
             raise HlAmdError(HL_AMD_ERROR_INVALID_FORMAT, "frame (picture size)")
 
     def encode_frame(self, frame: "Frame", ctl: "FrameCtl | None" = None) -> EncodeResult:

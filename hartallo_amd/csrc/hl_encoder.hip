@@ -13,7 +13,8 @@
 // Runs of pictures: k_pipeline (hl_pipeline.h), one persistent launch.
 // Spatial SVC layers: k_svc_mb, k_deblock_rows, k_el_count / k_el_write; the
 // lower layers' input from the top layer's frame: k_pyramid (hl_pyramid.h).
-// Frames that are not dense I420 (hl_amd_encode_frame): k_ingest (hl_ingest.h).
+// Frames that are not dense I420 (hl_amd_encode_frame): k_ingest (hl_ingest.h);
+// frames larger than the picture (hl_amd_set_source_size): k_scale (hl_scale.h).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -40,6 +41,7 @@
 #include "hl_scene.h"
 #include "hl_quality.h"
 #include "hl_ingest.h"
+#include "hl_scale.h"
 #include "hl_writer.h"
 #endif
 
@@ -1244,6 +1246,21 @@ struct hl_amd_encoder_s {
     std::vector<const uint8_t*> in_src;          // [3 k + c] the converted planes of its picture k, null: forwarded
     bool in_ok = false;                          // the last encode call was a frame call and ended well
     bool in_nested = false;                      // inside a frame call (encode_pictures keeps the above)
+    // frames larger than the picture (hl_amd_set_source_size, hl_scale.h): the
+    // ingest writes I420 planes of the source size into d_sk_src, k_scale
+    // writes the planes above from them
+    int32_t sW = 0, sH = 0;                      // the frames' size; 0, 0: none (the display size)
+    hl::SkParm sk_parm{};                        // ... and what its launches are given
+    uint8_t* d_sk_src = nullptr;                 // the call's frames at the source size rounded up to 16, Y | U | V each
+    size_t sk_src_cap = 0;
+    hl::SkFrame* d_sk_tab = nullptr;             // hl_amd_encode_frames: the frames of its scale launches
+    size_t sk_tab_cap = 0;
+    std::vector<hl::SkFrame> sk_tab;             // ... staged
+    struct SkLaunch {
+        hl::SkArgs A;
+        int frames;
+    };
+    std::vector<SkLaunch> sk_launches;           // the last frame call's scale launches (hl_amd_bench_scale)
 };
 
 static void svc_free(hl_amd_encoder_t* e);
@@ -1283,6 +1300,8 @@ static void free_all(hl_amd_encoder_t* e)
     (void)hipFree(e->d_stage);
     (void)hipFree(e->d_inb);
     (void)hipFree(e->d_in_tab);
+    (void)hipFree(e->d_sk_src);
+    (void)hipFree(e->d_sk_tab);
     (void)hipFree(e->d_bpic);
     (void)hipFree(e->d_bpl);
     (void)hipFree(e->d_brec);
@@ -2622,7 +2641,7 @@ extern "C" int32_t hl_amd_set_display_size(hl_amd_encoder_t* e, int32_t width, i
     if (!e) return HL_AMD_ERROR_INVALID_PARAMETER;
     if (e->svc) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // (the subset SPS is not touched)
     if (!display_size_ok(e->W, e->H, width, height)) return HL_AMD_ERROR_INVALID_PARAMETER;
-    if (e->frame_index != 0 || e->la_n) return HL_AMD_ERROR_INVALID_STATE;
+    if (e->frame_index != 0 || e->la_n || e->sW) return HL_AMD_ERROR_INVALID_STATE;  // (a source size is relative to the display size: set that first)
     e->dW = width;
     e->dH = height;
     rebuild_headers(e);
@@ -3017,7 +3036,7 @@ extern "C" int32_t hl_amd_encode_ex(hl_amd_encoder_t* e, const uint8_t* y, const
 // a dense I420 frame in device memory: coded from the caller's planes as it is
 static bool in_forwarded(const hl_amd_encoder_t* e, const hl_amd_frame_t& f)
 {
-    if (!f.on_device || f.format != HL_AMD_FORMAT_I420 || display_set(e)) return false;  // (a frame below the coded size is padded by k_ingest_edge)
+    if (!f.on_device || f.format != HL_AMD_FORMAT_I420 || display_set(e) || e->sW) return false;  // (a frame below the coded size is padded by k_ingest_edge, one above the display size scaled by k_scale)
     for (int c = 0; c < 3; ++c)
         if (f.pitch[c] && f.pitch[c] != in_row_bytes(IN_I420, c, e->W)) return false;
     return true;
@@ -3027,11 +3046,12 @@ static bool in_forwarded(const hl_amd_encoder_t* e, const hl_amd_frame_t& f)
 static int32_t check_frames(const hl_amd_encoder_t* e, const hl_amd_frame_t* f, int n, bool device_only)
 {
     const bool queued = !device_only && e->lookahead > 1;  // hl_amd_encode_frame with look-ahead: coded from the queue's copy
+    const int fW = e->sW ? e->sW : e->dW;                  // a frame has the source size, else the display size (the coded size unless one was set)
     for (int i = 0; i < n; ++i) {
         if (f[i].format < 0 || f[i].format >= IN_FORMATS) return HL_AMD_ERROR_INVALID_PARAMETER;
         if (device_only && !f[i].on_device) return HL_AMD_ERROR_INVALID_PARAMETER;
-        for (int c = 0; c < in_planes(f[i].format); ++c)  // (a frame has the display size: the coded size unless one was set)
-            if (!f[i].plane[c] || f[i].pitch[c] < 0 || (f[i].pitch[c] && f[i].pitch[c] < in_row_bytes(f[i].format, c, e->dW)))
+        for (int c = 0; c < in_planes(f[i].format); ++c)
+            if (!f[i].plane[c] || f[i].pitch[c] < 0 || (f[i].pitch[c] && f[i].pitch[c] < in_row_bytes(f[i].format, c, fW)))
                 return HL_AMD_ERROR_INVALID_PARAMETER;
         if (in_forwarded(e, f[i])) {  // the caller's planes are what scene-cut detection and quality read, unless the frame is queued
             if (!queued && (!quality_aligned(e, f[i].plane[0], f[i].plane[1], f[i].plane[2]) || (e->sc_thr && ((uintptr_t)f[i].plane[0] & 3))))
@@ -3039,7 +3059,7 @@ static int32_t check_frames(const hl_amd_encoder_t* e, const hl_amd_frame_t* f, 
         }
         else if (f[i].on_device) {  // k_ingest loads 4-byte words (a dense row of a display width like 34 is no multiple of 4)
             for (int c = 0; c < in_planes(f[i].format); ++c) {
-                const uint64_t pitch = f[i].pitch[c] ? (uint64_t)f[i].pitch[c] : (uint64_t)in_row_bytes(f[i].format, c, e->dW);
+                const uint64_t pitch = f[i].pitch[c] ? (uint64_t)f[i].pitch[c] : (uint64_t)in_row_bytes(f[i].format, c, fW);
                 if (((uintptr_t)f[i].plane[c] | pitch) & 3) return HL_AMD_ERROR_INVALID_PARAMETER;
             }
         }
@@ -3087,9 +3107,57 @@ static int32_t in_stage(hl_amd_encoder_t* e, const hl_amd_frame_t& f, int dW, in
     return HL_AMD_SUCCESS;
 }
 
+// the planes of frame k of d_sk_src (grown to hold n frames): the source size rounded up to 16
+static int32_t sk_source(hl_amd_encoder_t* e, size_t n, size_t k, uint8_t** p)
+{
+    const size_t ny = (size_t)e->sk_parm.sp * ((e->sH + 15) & ~15), fb = ny + ny / 2;
+    if (e->sk_src_cap < fb * n) {
+        (void)hipFree(e->d_sk_src);
+        e->d_sk_src = nullptr;
+        e->sk_src_cap = 0;
+        if (hipMalloc(&e->d_sk_src, fb * n) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e->sk_src_cap = fb * n;
+    }
+    p[0] = e->d_sk_src + fb * k;
+    p[1] = p[0] + ny;
+    p[2] = p[1] + ny / 4;
+    return HL_AMD_SUCCESS;
+}
+
+// one (checked) frame of the source size into the planes dst: the ingest into d_sk_src, then k_scale
+static int32_t sk_one(hl_amd_encoder_t* e, const hl_amd_frame_t& f, uint8_t* const* dst)
+{
+    uint8_t* mid[3];
+    int32_t rc = sk_source(e, 1, 0, mid);
+    if (rc) return rc;
+    InArgs A{};
+    if (f.on_device) A.one = in_describe(f, e->sW);
+    else {
+        rc = in_stage(e, f, e->sW, e->sH, &A.one);
+        if (rc) return rc;
+    }
+    SkArgs S{};
+    for (int c = 0; c < 3; ++c) {
+        S.one.src[c] = A.one.dst[c] = mid[c];
+        S.one.dst[c] = dst[c];
+    }
+    A.coef = in_coef_of(e->in_matrix, e->in_range);
+    A.W = e->sk_parm.sp;
+    A.H = (e->sH + 15) & ~15;
+    A.dW = e->sW;
+    A.dH = e->sH;
+    HL_HIP_CHECK(launch_ingest(A, f.format, 1, e->stream));
+    e->in_launches.push_back({A, f.format, 1});
+    S.parm = e->sk_parm;
+    HL_HIP_CHECK(launch_scale(S, 1, e->stream));
+    e->sk_launches.push_back({S, 1});
+    return HL_AMD_SUCCESS;
+}
+
 // one (checked, not forwarded) frame into the planes dst: the call's one launch
 static int32_t in_one(hl_amd_encoder_t* e, const hl_amd_frame_t& f, uint8_t* const* dst)
 {
+    if (e->sW) return sk_one(e, f, dst);
     InArgs A{};
     if (f.on_device) A.one = in_describe(f, e->dW);
     else {
@@ -3117,6 +3185,36 @@ extern "C" int32_t hl_amd_set_colour(hl_amd_encoder_t* e, int32_t matrix, int32_
     return HL_AMD_SUCCESS;
 }
 
+// The size of the frames the frame calls take from now on (no reference
+// interface: the reference has no scaler); the display size turns it off.
+extern "C" int32_t hl_amd_set_source_size(hl_amd_encoder_t* e, int32_t width, int32_t height)
+{
+    if (!e) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->svc) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // (the layers' input is k_pyramid's)
+    SkParm P{};
+    if (width <= 0 || height <= 0 || width > kSkMaxSource || height > kSkMaxSource || !sk_parm(width, height, (width + 15) & ~15, e->dW, e->dH, e->W, e->H, &P)) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->la_n) return HL_AMD_ERROR_INVALID_STATE;  // queued frames come first (hl_amd_flush)
+    const bool off = width == e->dW && height == e->dH;
+    e->sW = off ? 0 : width;
+    e->sH = off ? 0 : height;
+    e->sk_parm = P;
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_get_source_size(hl_amd_encoder_t* e, int32_t* width, int32_t* height)
+{
+    if (!e || !width || !height) return HL_AMD_ERROR_INVALID_PARAMETER;
+    *width = e->sW ? e->sW : e->dW;
+    *height = e->sW ? e->sH : e->dH;
+    return HL_AMD_SUCCESS;
+}
+
+// the taps of output j of the axis s -> d (a pure function; no device)
+extern "C" int32_t hl_amd_scale_taps(int32_t s, int32_t d, int32_t j, int32_t* first, uint32_t* weights, int32_t cap)
+{
+    return sk_taps(s, d, j, first, weights, cap);
+}
+
 extern "C" int32_t hl_amd_encode_frame(hl_amd_encoder_t* e, const hl_amd_frame_t* f, const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* r)
 {
     if (!e || !f || !r) return HL_AMD_ERROR_INVALID_PARAMETER;
@@ -3130,6 +3228,7 @@ extern "C" int32_t hl_amd_encode_frame(hl_amd_encoder_t* e, const hl_amd_frame_t
     const bool fwd = in_forwarded(e, *f);
     const size_t ny = (size_t)e->W * e->H, nc = (size_t)e->Wc * e->Hc, fb = ny + 2 * nc;
     e->in_launches.clear();
+    e->sk_launches.clear();
     e->in_max_margin = 16;
     e->in_src.assign(3, nullptr);
     if (e->lookahead > 1) {  // as hl_amd_encode_ex: the frame goes into the queue's next slot, a full queue is coded
@@ -3201,8 +3300,22 @@ extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl
         if (hipMalloc(&e->d_in_tab, sizeof(InFrame) * m) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
         e->in_tab_cap = m;
     }
+    if (e->sW) {  // (every frame is converted: m = n)
+        uint8_t* mid[3];
+        rc = sk_source(e, m, 0, mid);
+        if (rc) return rc;
+        if (e->sk_tab_cap < m) {
+            (void)hipFree(e->d_sk_tab);
+            e->d_sk_tab = nullptr;
+            e->sk_tab_cap = 0;
+            if (hipMalloc(&e->d_sk_tab, sizeof(SkFrame) * m) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+            e->sk_tab_cap = m;
+        }
+    }
     // the table, format by format (one launch per format); frame i keeps its place in the call
     e->in_launches.clear();
+    e->sk_launches.clear();
+    e->sk_tab.clear();
     e->in_max_margin = 16;
     e->in_src.assign((size_t)3 * n, nullptr);
     e->in_tab.clear();
@@ -3212,11 +3325,20 @@ extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl
         first[fmt] = e->in_tab.size();
         for (int i = 0; i < n; ++i) {
             if (f[i].format != fmt || in_forwarded(e, f[i])) continue;
-            InFrame F = in_describe(f[i], e->dW);
+            InFrame F = in_describe(f[i], e->sW ? e->sW : e->dW);
             uint8_t* d = e->d_inb + fb * e->in_tab.size();
             y[i] = e->in_src[3 * (size_t)i] = F.dst[0] = d;
             u[i] = e->in_src[3 * (size_t)i + 1] = F.dst[1] = d + ny;
             v[i] = e->in_src[3 * (size_t)i + 2] = F.dst[2] = d + ny + nc;
+            if (e->sW) {  // the ingest writes the frame's planes of d_sk_src, k_scale the planes above from them
+                SkFrame S{};
+                (void)sk_source(e, m, e->in_tab.size(), F.dst);  // (grown above)
+                for (int c = 0; c < 3; ++c) S.src[c] = F.dst[c];
+                S.dst[0] = d;
+                S.dst[1] = d + ny;
+                S.dst[2] = d + ny + nc;
+                e->sk_tab.push_back(S);
+            }
             e->in_tab.push_back(F);
         }
     }
@@ -3233,14 +3355,25 @@ extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl
             InArgs A{};
             A.tab = e->d_in_tab + f0;
             A.coef = in_coef_of(e->in_matrix, e->in_range);
-            A.W = e->W;
-            A.H = e->H;
-            A.dW = e->dW;
-            A.dH = e->dH;
+            A.W = e->sW ? e->sk_parm.sp : e->W;
+            A.H = e->sW ? (e->sH + 15) & ~15 : e->H;
+            A.dW = e->sW ? e->sW : e->dW;
+            A.dH = e->sW ? e->sH : e->dH;
             const int frames = (int)std::min<size_t>(65535, first[fmt + 1] - f0);
             HL_HIP_CHECK(launch_ingest(A, fmt, frames, e->stream));
             e->in_launches.push_back({A, fmt, frames});
         }
+    if (e->sW) {  // every frame of the call, whatever its format
+        HL_HIP_CHECK(hipMemcpyAsync(e->d_sk_tab, e->sk_tab.data(), sizeof(SkFrame) * m, hipMemcpyHostToDevice, e->stream));
+        for (size_t f0 = 0; f0 < m; f0 += 65535) {  // grid z holds the frames
+            SkArgs S{};
+            S.tab = e->d_sk_tab + f0;
+            S.parm = e->sk_parm;
+            const int frames = (int)std::min<size_t>(65535, m - f0);
+            HL_HIP_CHECK(launch_scale(S, frames, e->stream));
+            e->sk_launches.push_back({S, frames});
+        }
+    }
     e->in_nested = true;
     rc = encode_pictures(e, n, y.data(), u.data(), v.data(), results, ctl);
     e->in_nested = false;
@@ -3276,6 +3409,29 @@ extern "C" int32_t hl_amd_bench_ingest(hl_amd_encoder_t* e, int32_t iters, float
     HL_HIP_CHECK(hipEventRecord(a, e->stream));
     for (int i = 0; i < iters; ++i)
         for (const auto& L : e->in_launches) HL_HIP_CHECK(launch_ingest(L.A, L.fmt, L.frames, e->stream, e->in_max_margin));
+    HL_HIP_CHECK(hipEventRecord(b, e->stream));
+    HL_HIP_CHECK(hipEventSynchronize(b));
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, a, b);
+    *ms = t / iters;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return HL_AMD_SUCCESS;
+}
+
+// k_scale alone: `iters` times the scale launches of the last frame call (the
+// same intermediate planes into the same planes), timed like hl_amd_bench_ingest.
+extern "C" int32_t hl_amd_bench_scale(hl_amd_encoder_t* e, int32_t iters, float* ms)
+{
+    if (!e || iters <= 0 || !ms) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->in_ok || e->sk_launches.empty()) return HL_AMD_ERROR_INVALID_STATE;
+    hipEvent_t a, b;
+    HL_HIP_CHECK(hipEventCreate(&a));
+    HL_HIP_CHECK(hipEventCreate(&b));
+    for (const auto& L : e->sk_launches) HL_HIP_CHECK(launch_scale(L.A, L.frames, e->stream));  // warm
+    HL_HIP_CHECK(hipEventRecord(a, e->stream));
+    for (int i = 0; i < iters; ++i)
+        for (const auto& L : e->sk_launches) HL_HIP_CHECK(launch_scale(L.A, L.frames, e->stream));
     HL_HIP_CHECK(hipEventRecord(b, e->stream));
     HL_HIP_CHECK(hipEventSynchronize(b));
     float t = 0.f;
@@ -3835,6 +3991,7 @@ static int32_t svc_join(hl_amd_encoder_t* e, int upto)
 extern "C" int32_t hl_amd_add_layer(hl_amd_encoder_t* e, int32_t width, int32_t height)
 {
     if (!e || width <= 0 || height <= 0) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (e->sW) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // hl_amd_set_source_size is AVC only (the layers have k_pyramid), at any time
     if (e->frame_index > 0 || e->la_n || (e->svc && e->svc->started)) return HL_AMD_ERROR_INVALID_STATE;
     if (display_set(e)) return HL_AMD_ERROR_NOT_IMPLEMENTED;  // hl_amd_set_display_size is AVC only (the subset SPS carries no cropping)
     e->lookahead = 1;  // (the look-ahead is AVC only: an encoder with layers ignores it)

@@ -802,6 +802,70 @@ int32_t hl_amd_get_input(hl_amd_encoder_t* encoder, int32_t k, uint8_t* y, uint8
  * interface (like hl_amd_bench_pyramid). */
 int32_t hl_amd_bench_ingest(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
 
+/* ---- frames larger than the picture ----
+ * No reference interface: the reference has no scaler (test_encoder.c:100-111
+ * reads one pre-scaled file per layer).  With a source size sw x sh the frames
+ * of hl_amd_encode_frame / hl_amd_encode_frames have that size and are scaled
+ * on the GPU to the display size dw x dh (the coded size unless one was set)
+ * by an area filter defined in integers (hartallo_amd/csrc/hl_scale.h).  Per
+ * axis, with a source length s and a destination length d, d <= s <= 8 d:
+ * g = gcd(s, d), sr = s / g, dr = d / g; output sample j covers
+ * [j sr, (j + 1) sr), source sample i covers [i dr, (i + 1) dr), and
+ *   w(j, i) = max(0, min((j + 1) sr, (i + 1) dr) - max(j sr, i dr));
+ * the taps of j are i = floor(j sr / dr) .. floor(((j + 1) sr - 1) / dr), at
+ * most ceil(sr / dr) + 1 <= 9, every weight positive, their sum sr.  A plane,
+ * with D = srw srh:
+ *   out(x, y) = floor((sum_k sum_i wv(y, k) wh(x, i) p(k, i) + (D >> 1)) / D):
+ * separable, unrounded, rounded once, half up; every quantity fits 32
+ * unsigned bits.  Luma goes sw x sh -> dw x dh; U and V go sw/2 x sh/2 ->
+ * dw/2 x dh/2 by the same formulas (chroma stays centre-sited, as in the
+ * ingest).  Beyond the display size the coded planes take
+ * out(min(x, dw - 1), min(y, dh - 1)): the display size's edge replication.
+ * 2:1 on both axes is the 2x2 box of k_pyramid (the SVC layers' filter) bit
+ * for bit; 4:1 is NOT that box applied twice, which rounds at each stage (on a
+ * 96x64 noise plane 77 of the 384 samples differ).
+ * Data path: the frame goes through k_ingest at the source size -- formats,
+ * colour tables, the 4-byte rule of device planes and the read contract hold
+ * with W, H = sw, sh -- into an intermediate I420 buffer the encoder owns, and
+ * k_scale writes the encoder's input planes (the look-ahead slot, the frame's
+ * planes of hl_amd_encode_frames) from it.  Nothing is forwarded.  Scene cuts,
+ * quality (source = the scaled planes), rate control, the GOP counter and the
+ * look-ahead see planes of the coded size; hl_amd_get_input returns the scaled,
+ * padded planes: what was encoded.  The plain entry points (hl_amd_encode,
+ * _device, _batch, _streams, the _ex forms, hl_amd_encode_au*) keep taking
+ * planes of the coded size. */
+
+/* The size of the frames from now on: even, dw <= width <= min(8 dw, 4096),
+ * dh <= height <= min(8 dh, 4096), else HL_AMD_ERROR_INVALID_PARAMETER;
+ * (dw, dh) turns scaling off, and the path is then the one without this call,
+ * forwarding of dense I420 device frames included.  Between any two encode
+ * calls (a source may change its resolution mid-stream), like
+ * hl_amd_set_colour; HL_AMD_ERROR_INVALID_STATE while look-ahead frames are
+ * queued; HL_AMD_ERROR_NOT_IMPLEMENTED on an encoder with spatial layers, and
+ * from hl_amd_add_layer once a source size is set.  Set the display size
+ * first: hl_amd_set_display_size returns HL_AMD_ERROR_INVALID_STATE while a
+ * source size is set.  No reference interface (see above). */
+int32_t hl_amd_set_source_size(hl_amd_encoder_t* encoder, int32_t width, int32_t height);
+
+/* The size of the frame calls' frames: the source size, else the display
+ * size.  No reference interface (see above). */
+int32_t hl_amd_get_source_size(hl_amd_encoder_t* encoder, int32_t* width, int32_t* height);
+
+/* The taps of output sample j of the axis s -> d (a pure function, no device,
+ * like hl_amd_stream_headers): *first = the first source sample, weights[0 ..
+ * count) its and its successors' weights; returns the count (1..9), or 0 for
+ * what it refuses: s < d, s > 8 d, s > 4096, d <= 0, j outside [0, d), cap
+ * below the count, a null pointer.  s and d may be odd (a chroma axis is).
+ * No reference interface (see above). */
+int32_t hl_amd_scale_taps(int32_t s, int32_t d, int32_t j, int32_t* first, uint32_t* weights, int32_t cap);
+
+/* Diagnostics: `iters` times the k_scale launch(es) of the last frame call
+ * (the same intermediate planes into the same planes); *ms = average ms per
+ * repetition.  hl_amd_bench_ingest keeps repeating the ingest launches only.
+ * HL_AMD_ERROR_INVALID_STATE when that call scaled nothing or did not
+ * succeed.  No reference interface (like hl_amd_bench_ingest). */
+int32_t hl_amd_bench_scale(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
+
 /* device time (ms) of the enhancement layers of the last access unit (with
  * hl_amd_set_timing on) */
 float hl_amd_svc_layer_ms(hl_amd_encoder_t* encoder);
