@@ -7,6 +7,7 @@
 #   tests/emu/libhl_ingest_emu.so    test-only host build of the frame ingest (hl_ingest.h)
 #   tests/emu/libhl_display_emu.so   test-only host build of the display size's edge tiles and quality window (hl_ingest.h, hl_quality.h)
 #   tests/emu/libhl_scale_emu.so     test-only host build of the area downscaler behind the ingest (hl_scale.h, hl_ingest.h)
+#   tests/emu/libhl_ladder_emu.so    test-only host build of the rendition ladder's fan-out behind one ingest (hl_ladder.h, hl_ingest.h)
 #   tests/emu/libhl_svc_display_emu.so  test-only host build of the ingest's edge tiles with margins wider than a macroblock (hl_ingest.h)
 #   tests/emu/libhl_svc_geom_emu.so  test-only host exports of the enhancement layers' constants and Intra_Base sample (hl_svc.h)
 #   tests/emu/libhl_sched_emu.so     test-only host build of the pipelined run's pop (hl_sched.h)
@@ -32,14 +33,14 @@ CXXFLAGS := -std=c++17 -O3 -fPIC -ffp-contract=off -Wall -Wno-unused-function -W
 DEVFLAGS := -mllvm -amdgpu-sched-strategy=iterative-ilp
 # k_ingest (hl_ingest.hip) is compiled on its own, without DEVFLAGS: that
 # strategy crashes the compiler's register allocator on the planar-RGB kernel
-# k_scale (hl_scale.hip) likewise: bandwidth-bound, nothing to gain from that strategy
-INGOBJ  := build/obj/hl_ingest.o build/obj/hl_scale.o
+# k_scale (hl_scale.hip) and k_scale_fan (hl_ladder.hip) likewise: bandwidth-bound, nothing to gain from that strategy
+INGOBJ  := build/obj/hl_ingest.o build/obj/hl_scale.o build/obj/hl_ladder.o
 
 .PHONY: all product emu unit oracle profile poison variant sanitize ubsan clean
 all: product emu unit oracle sanitize
 
 product: hartallo_amd/libhartallo_amd.so
-emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_display_emu.so tests/emu/libhl_scale_emu.so tests/emu/libhl_svc_display_emu.so tests/emu/libhl_svc_geom_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so
+emu: tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_display_emu.so tests/emu/libhl_scale_emu.so tests/emu/libhl_ladder_emu.so tests/emu/libhl_svc_display_emu.so tests/emu/libhl_svc_geom_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so
 unit: tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so
 
 build/obj/hl_ingest.o: $(CSRC)/hl_ingest.hip $(CSRC)/hl_ingest.h
@@ -49,6 +50,10 @@ build/obj/hl_ingest.o: $(CSRC)/hl_ingest.hip $(CSRC)/hl_ingest.h
 build/obj/hl_scale.o: $(CSRC)/hl_scale.hip $(CSRC)/hl_scale.h
 	mkdir -p build/obj
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c -o $@ $(CSRC)/hl_scale.hip
+
+build/obj/hl_ladder.o: $(CSRC)/hl_ladder.hip $(CSRC)/hl_ladder.h $(CSRC)/hl_scale.h
+	mkdir -p build/obj
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c -o $@ $(CSRC)/hl_ladder.hip
 
 hartallo_amd/libhartallo_amd.so: $(KSRC) $(HOSTSRC) $(HDRS) $(INGOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(DEVFLAGS) -shared -o $@ $(KSRC) $(HOSTSRC) -x none $(INGOBJ)
@@ -84,6 +89,10 @@ tests/emu/libhl_display_emu.so: tests/emu/hl_display_emu.cpp $(CSRC)/hl_ingest.h
 # the area downscaler behind the ingest on the host: k_scale's per-lane functions looped over a frame (no device code)
 tests/emu/libhl_scale_emu.so: tests/emu/hl_scale_emu.cpp $(CSRC)/hl_scale.h $(CSRC)/hl_ingest.h
 	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_scale_emu.cpp
+
+# the rendition ladder on the host: one ingest at the source size, then k_scale_fan's block selection and per-lane functions looped over a launch (no device code)
+tests/emu/libhl_ladder_emu.so: tests/emu/hl_ladder_emu.cpp $(CSRC)/hl_ladder.h $(CSRC)/hl_scale.h $(CSRC)/hl_ingest.h
+	$(CXX) -std=c++17 -O2 -fPIC -Wall -shared -o $@ tests/emu/hl_ladder_emu.cpp
 
 # the access unit's display size on the host: the ingest's tiles with margins up to (16 << K) - 2 (no device code)
 tests/emu/libhl_svc_display_emu.so: tests/emu/hl_svc_display_emu.cpp $(CSRC)/hl_ingest.h
@@ -130,11 +139,13 @@ tests/gpu_unit/libhl_unit_rec.so: tests/gpu_unit/hl_unit_rec.hip $(HDRS)
 #   tests/sanitize/scale_asan  the area downscaler behind the ingest (hl_scale.h):
 #       exactly-sized source planes, every output sample against a scalar
 #       statement of the definition
+#   tests/sanitize/ladder_asan  the rendition ladder's fan-out (hl_ladder.h): the
+#       same for every rung of a launch, the LDS image sized for the launch's maximum
 # (hipcc: every -fsanitize= directly after -Xarch_host, host code only)
 SANFLAGS := -std=c++17 -O1 -g -fno-omit-frame-pointer -fPIC -ffp-contract=off -Wno-unused-function -Wno-unused-variable
 ASAN := -Xarch_host -fsanitize=address
 UBSAN := -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined
-sanitize: tests/sanitize/libhl_emu_asan.so tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan tests/sanitize/ingest_edge_asan tests/sanitize/ingest_wide_asan tests/sanitize/scale_asan
+sanitize: tests/sanitize/libhl_emu_asan.so tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan tests/sanitize/ingest_edge_asan tests/sanitize/ingest_wide_asan tests/sanitize/scale_asan tests/sanitize/ladder_asan
 tests/sanitize/hl_writer_asan.o: $(CSRC)/hl_writer.cpp $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) $(SANFLAGS) $(ASAN) $(UBSAN) -c -o $@ $<
 tests/sanitize/hl_rc_asan.o: $(CSRC)/hl_rc.cpp $(HDRS)
@@ -155,6 +166,8 @@ tests/sanitize/ingest_wide_asan: tests/sanitize/ingest_wide_asan.cpp $(CSRC)/hl_
 	$(HIPCC) $(SANFLAGS) $(ASAN) $(UBSAN) -o $@ -x c++ tests/sanitize/ingest_wide_asan.cpp
 tests/sanitize/scale_asan: tests/sanitize/scale_asan.cpp $(CSRC)/hl_scale.h $(CSRC)/hl_ingest.h
 	$(HIPCC) $(SANFLAGS) $(ASAN) $(UBSAN) -o $@ -x c++ tests/sanitize/scale_asan.cpp
+tests/sanitize/ladder_asan: tests/sanitize/ladder_asan.cpp $(CSRC)/hl_ladder.h $(CSRC)/hl_scale.h $(CSRC)/hl_ingest.h
+	$(HIPCC) $(SANFLAGS) $(ASAN) $(UBSAN) -o $@ -x c++ tests/sanitize/ladder_asan.cpp
 # the emulator under UndefinedBehaviorSanitizer too: a 16-minute compile of
 # the kernel logic, run once per change of the shift / overflow idioms
 # (DESIGN.md §2); tests/test_sanitizers.py uses it when it is present
@@ -197,5 +210,5 @@ oracle: product  # oracle/_ref/drop_in_enc links the product library
 	if [ -f oracle/_ref/libhl.a ] && [ -d $(REF)/source ]; then $(MAKE) -C tests/refdrive REF=$(REF); fi
 
 clean:
-	rm -f $(INGOBJ) tests/emu/libhl_scale_emu.so tests/sanitize/scale_asan hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_display_emu.so tests/emu/libhl_svc_display_emu.so tests/emu/libhl_svc_geom_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan tests/sanitize/ingest_edge_asan tests/sanitize/ingest_wide_asan
+	rm -f $(INGOBJ) tests/emu/libhl_scale_emu.so tests/emu/libhl_ladder_emu.so tests/sanitize/scale_asan tests/sanitize/ladder_asan hartallo_amd/libhartallo_amd.so tests/emu/libhl_emu.so tests/emu/libhl_pyr_emu.so tests/emu/libhl_scene_emu.so tests/emu/libhl_quality_emu.so tests/emu/libhl_ingest_emu.so tests/emu/libhl_display_emu.so tests/emu/libhl_svc_display_emu.so tests/emu/libhl_svc_geom_emu.so tests/emu/libhl_rec_emu.so tests/emu/libhl_sched_emu.so tests/gpu_unit/libhl_unit.so tests/gpu_unit/libhl_unit_cand.so tests/gpu_unit/libhl_unit_rec.so tests/sanitize/*.so tests/sanitize/*.o tests/sanitize/rowgate_tsan tests/sanitize/pop_tsan tests/sanitize/ingest_asan tests/sanitize/ingest_edge_asan tests/sanitize/ingest_wide_asan
 	$(MAKE) -C oracle clean

@@ -119,6 +119,9 @@ EXPORTED_SYMBOLS = (
     "hl_amd_get_source_size",
     "hl_amd_scale_taps",
     "hl_amd_bench_scale",
+    "hl_amd_encode_ladder_frame",
+    "hl_amd_encode_ladder_frames",
+    "hl_amd_bench_ladder",
     "hl_amd_set_au_display_size",
     "hl_amd_get_au_display_size",
     "hl_amd_svc_stream_headers",
@@ -564,6 +567,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         if hasattr(lib, name):  # (absent from builds before the source size loaded through HL_LIB)
             getattr(lib, name).argtypes = args
             getattr(lib, name).restype = i32
+    pvp = ctypes.POINTER(ctypes.c_void_p)
+    for name, args in (("hl_amd_encode_ladder_frame", [pvp, i32, pf, pc, ctypes.POINTER(_Result)]),
+                       ("hl_amd_encode_ladder_frames", [pvp, i32, i32, pf, pc, ctypes.POINTER(_Result)]),
+                       ("hl_amd_bench_ladder", [vp, i32, ctypes.POINTER(ctypes.c_float)])):
+        if hasattr(lib, name):  # (absent from builds before the rendition ladder loaded through HL_LIB)
+            getattr(lib, name).argtypes = args
+            getattr(lib, name).restype = i32
     if hasattr(lib, "hl_amd_svc_stream_headers"):
         lib.hl_amd_svc_stream_headers.argtypes = [ctypes.POINTER(_Params), i32, i32, i32, i32, vp, ctypes.c_size_t]
         lib.hl_amd_svc_stream_headers.restype = ctypes.c_size_t
@@ -886,6 +896,70 @@ class Encoder:
         rc = self.lib.hl_amd_bench_scale(self._h, iters, ctypes.byref(ms))
         if rc:
             raise HlAmdError(rc, "hl_amd_bench_scale")
+        return ms.value
+
+    @staticmethod
+    def _ladder_ctl(ctl, count, n):
+        """per rung a list of n FrameCtl objects -> the call's C array, ctl[r * n + i]"""
+        if ctl is None:
+            return None
+        if len(ctl) != count:
+            raise HlAmdError(HL_AMD_ERROR_INVALID_PARAMETER, "ctl (one list per rung)")
+        for c in ctl:
+            _ctl_array(c, n)  # (one per frame)
+        return _ctl_array([c for cs in ctl for c in cs], count * n)
+
+    @staticmethod
+    def encode_ladder_frame(encoders, frame: "Frame", ctl=None):
+        """One frame of the encoders' common source size, converted once and
+        scaled for every encoder (a "rung") by one GPU launch, then coded by
+        each as encode_frame codes it (hl_amd_encode_ladder_frame).  ctl: one
+        FrameCtl per rung.  Returns one EncodeResult per rung."""
+        count = len(encoders)
+        if count and frame.width and any((frame.width, frame.height) != e.source_size for e in encoders):
+            raise HlAmdError(HL_AMD_ERROR_INVALID_FORMAT, "frame (picture size)")
+        lib = encoders[0].lib if count else load_library()
+        hs = (ctypes.c_void_p * max(count, 1))(*[e._h for e in encoders])
+        res = (_Result * max(count, 1))()
+        c = frame._c()
+        rc = lib.hl_amd_encode_ladder_frame(hs, count, ctypes.byref(c), Encoder._ladder_ctl([[x] for x in ctl] if ctl is not None else None, count, 1), res)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_ladder_frame")
+        return [e._result(res[r]) for r, e in enumerate(encoders)]
+
+    @staticmethod
+    def encode_ladder_frames_device(encoders, frames, ctl=None, collect: bool = True):
+        """Consecutive device frames of the encoders' common source size,
+        converted once and scaled for every rung by one GPU launch, then coded
+        rung after rung as encode_frames_device codes them
+        (hl_amd_encode_ladder_frames).  ctl: per rung a list of one FrameCtl
+        per frame.  Returns per rung its results (or, with collect=False, its
+        total bitstream bytes)."""
+        count, n = len(encoders), len(frames)
+        for f in frames:
+            if count and f.width and any((f.width, f.height) != e.source_size for e in encoders):
+                raise HlAmdError(HL_AMD_ERROR_INVALID_FORMAT, "frame (picture size)")
+        lib = encoders[0].lib if count else load_library()
+        hs = (ctypes.c_void_p * max(count, 1))(*[e._h for e in encoders])
+        arr = (_Frame * max(n, 1))(*[f._c() for f in frames])
+        res = (_Result * max(count * n, 1))()
+        rc = lib.hl_amd_encode_ladder_frames(hs, count, n, arr, Encoder._ladder_ctl(ctl, count, n), res)
+        if rc != HL_AMD_SUCCESS:
+            raise HlAmdError(rc, "hl_amd_encode_ladder_frames")
+        out = []
+        for r, e in enumerate(encoders):
+            rs = res[r * n:(r + 1) * n]
+            e._last_batch = rs
+            out.append([e._result(x) for x in rs] if collect else sum(x.data_size for x in rs))
+        return out
+
+    def bench_ladder(self, iters: int = 50) -> float:
+        """average ms of the k_scale_fan launch(es) of the last ladder call,
+        whose first encoder this is (diagnostics)"""
+        ms = ctypes.c_float()
+        rc = self.lib.hl_amd_bench_ladder(self._h, iters, ctypes.byref(ms))
+        if rc:
+            raise HlAmdError(rc, "hl_amd_bench_ladder")
         return ms.value
 
     def _check_frame(self, f: "Frame"):

@@ -14,7 +14,8 @@
 // Spatial SVC layers: k_svc_mb, k_deblock_rows, k_el_count / k_el_write; the
 // lower layers' input from the top layer's frame: k_pyramid (hl_pyramid.h).
 // Frames that are not dense I420 (hl_amd_encode_frame): k_ingest (hl_ingest.h);
-// frames larger than the picture (hl_amd_set_source_size): k_scale (hl_scale.h).
+// frames larger than the picture (hl_amd_set_source_size): k_scale (hl_scale.h);
+// one source for several encoders (hl_amd_encode_ladder_frame): k_scale_fan (hl_ladder.h).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,6 +43,7 @@
 #include "hl_quality.h"
 #include "hl_ingest.h"
 #include "hl_scale.h"
+#include "hl_ladder.h"
 #include "hl_writer.h"
 #endif
 
@@ -1261,6 +1263,14 @@ struct hl_amd_encoder_s {
         int frames;
     };
     std::vector<SkLaunch> sk_launches;           // the last frame call's scale launches (hl_amd_bench_scale)
+    // one source for several encoders (hl_amd_encode_ladder_frame(s), hl_ladder.h):
+    // kept by the call's first encoder, whose d_sk_src and d_sk_tab hold the source
+    struct LdLaunch {
+        hl::LdArgs A;
+        int frames;
+    };
+    std::vector<LdLaunch> ld_launches;           // the last ladder call's fan-out launches (hl_amd_bench_ladder)
+    std::vector<hl_amd_encoder_s*> ld_rungs;     // ... and its encoders
 };
 
 static void svc_free(hl_amd_encoder_t* e);
@@ -3229,6 +3239,7 @@ extern "C" int32_t hl_amd_encode_frame(hl_amd_encoder_t* e, const hl_amd_frame_t
     const size_t ny = (size_t)e->W * e->H, nc = (size_t)e->Wc * e->Hc, fb = ny + 2 * nc;
     e->in_launches.clear();
     e->sk_launches.clear();
+    e->ld_launches.clear();  // (hl_amd_bench_ladder: this call may move the buffers a ladder call's launches read)
     e->in_max_margin = 16;
     e->in_src.assign(3, nullptr);
     if (e->lookahead > 1) {  // as hl_amd_encode_ex: the frame goes into the queue's next slot, a full queue is coded
@@ -3315,6 +3326,7 @@ extern "C" int32_t hl_amd_encode_frames(hl_amd_encoder_t* e, int32_t n, const hl
     // the table, format by format (one launch per format); frame i keeps its place in the call
     e->in_launches.clear();
     e->sk_launches.clear();
+    e->ld_launches.clear();  // (hl_amd_bench_ladder: this call may move the buffers a ladder call's launches read)
     e->sk_tab.clear();
     e->in_max_margin = 16;
     e->in_src.assign((size_t)3 * n, nullptr);
@@ -3432,6 +3444,289 @@ extern "C" int32_t hl_amd_bench_scale(hl_amd_encoder_t* e, int32_t iters, float*
     HL_HIP_CHECK(hipEventRecord(a, e->stream));
     for (int i = 0; i < iters; ++i)
         for (const auto& L : e->sk_launches) HL_HIP_CHECK(launch_scale(L.A, L.frames, e->stream));
+    HL_HIP_CHECK(hipEventRecord(b, e->stream));
+    HL_HIP_CHECK(hipEventSynchronize(b));
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, a, b);
+    *ms = t / iters;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return HL_AMD_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------
+// A rendition ladder from one source (hl_amd_encode_ladder_frame(s); no
+// reference interface: the reference has no scaler).  The frame(s) go once
+// through the staging and k_ingest at the common source size into
+// encoders[0]'s d_sk_src on its stream, k_scale_fan (hl_ladder.h) writes every
+// rung's coded planes -- d_in, or the rung's d_inb -- from it, the stream is
+// drained, and the rungs are coded one after another by encode_pictures, each
+// on its own stream and state: every rule of the per-encoder calls is theirs.
+// ---------------------------------------------------------------------------
+// the frames of a ladder call: check_frames' rules at the source size; nothing is forwarded
+static int32_t ld_check_frames(const hl_amd_frame_t* f, int n, int sw, bool device_only)
+{
+    for (int i = 0; i < n; ++i) {
+        if (f[i].format < 0 || f[i].format >= IN_FORMATS) return HL_AMD_ERROR_INVALID_PARAMETER;
+        if (device_only && !f[i].on_device) return HL_AMD_ERROR_INVALID_PARAMETER;
+        for (int c = 0; c < in_planes(f[i].format); ++c) {
+            const int64_t rb = in_row_bytes(f[i].format, c, sw);
+            if (!f[i].plane[c] || f[i].pitch[c] < 0 || (f[i].pitch[c] && f[i].pitch[c] < rb)) return HL_AMD_ERROR_INVALID_PARAMETER;
+            const uint64_t pitch = f[i].pitch[c] ? (uint64_t)f[i].pitch[c] : (uint64_t)rb;
+            if (f[i].on_device && (((uintptr_t)f[i].plane[c] | pitch) & 3)) return HL_AMD_ERROR_INVALID_PARAMETER;  // k_ingest loads 4-byte words
+        }
+    }
+    return HL_AMD_SUCCESS;
+}
+
+// Everything a ladder call is refused for, before anything is uploaded,
+// converted or launched (include/hartallo_amd.h); parm[r]: rung r's scale
+static int32_t ld_check(hl_amd_encoder_t* const* E, int count, int n, const hl_amd_frame_t* f, const hl_amd_frame_ctl_t* ctl,
+                        const hl_amd_result_t* results, bool single, SkParm* parm)
+{
+    if (!E || count < 1 || count > kLdMaxRungs || n <= 0 || !f || !results) return HL_AMD_ERROR_INVALID_PARAMETER;
+    for (int r = 0; r < count; ++r) {
+        if (!E[r]) return HL_AMD_ERROR_INVALID_PARAMETER;
+        for (int t = 0; t < r; ++t)
+            if (E[t] == E[r]) return HL_AMD_ERROR_INVALID_PARAMETER;
+    }
+    for (int r = 0; r < count; ++r) {  // as the per-encoder calls: a refused or failed call leaves no results
+        E[r]->in_ok = false;
+        if (!single || E[r]->lookahead <= 1) quality_drop(E[r]);
+    }
+    for (int r = 0; r < count; ++r)
+        if (E[r]->p.device != E[0]->p.device) return HL_AMD_ERROR_INVALID_PARAMETER;
+    for (int r = 0; r < count; ++r)
+        if (E[r]->svc) return HL_AMD_ERROR_NOT_IMPLEMENTED;
+    const int sw = E[0]->sW ? E[0]->sW : E[0]->dW, sh = E[0]->sW ? E[0]->sH : E[0]->dH;
+    for (int r = 0; r < count; ++r) {
+        const hl_amd_encoder_t* e = E[r];
+        if ((e->sW ? e->sW : e->dW) != sw || (e->sW ? e->sH : e->dH) != sh) return HL_AMD_ERROR_INVALID_PARAMETER;
+        if (e->in_matrix != E[0]->in_matrix || e->in_range != E[0]->in_range) return HL_AMD_ERROR_INVALID_PARAMETER;
+        // (a rung with a source size: what its hl_amd_set_source_size derived; an identity rung: s = d)
+        if (sw > kSkMaxSource || sh > kSkMaxSource || !sk_parm(sw, sh, (sw + 15) & ~15, e->dW, e->dH, e->W, e->H, &parm[r])) return HL_AMD_ERROR_INVALID_PARAMETER;
+    }
+    int32_t rc = ld_check_frames(f, n, sw, !single);
+    if (rc) return rc;
+    for (int r = 0; r < count; ++r)
+        if (E[r]->la_n || (single && E[r]->lookahead > 1)) return HL_AMD_ERROR_INVALID_STATE;  // look-ahead ladders are left out
+    for (int r = 0; r < count && ctl; ++r) {
+        rc = check_ctl(E[r], ctl + (size_t)r * n, n);
+        if (rc) return rc;
+    }
+    for (int r = 0; r < count; ++r)
+        if (E[r]->broken) return HL_AMD_ERROR_INVALID_STATE;
+    return HL_AMD_SUCCESS;
+}
+
+// the planes of frame k of e's d_sk_src, grown to hold n frames of the pitch sp and sh rows rounded up to 16 (sk_source's layout)
+static int32_t ld_source(hl_amd_encoder_t* e, int sp, int sh, size_t n, size_t k, uint8_t** p)
+{
+    const size_t ny = (size_t)sp * ((sh + 15) & ~15), fb = ny + ny / 2;
+    if (e->sk_src_cap < fb * n) {
+        (void)hipFree(e->d_sk_src);
+        e->d_sk_src = nullptr;
+        e->sk_src_cap = 0;
+        if (hipMalloc(&e->d_sk_src, fb * n) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e->sk_src_cap = fb * n;
+    }
+    p[0] = e->d_sk_src + fb * k;
+    p[1] = p[0] + ny;
+    p[2] = p[1] + ny / 4;
+    return HL_AMD_SUCCESS;
+}
+
+// a (checked) ladder call's launches are recorded; every encoder starts a frame call
+static void ld_begin(hl_amd_encoder_t* const* E, int count, int n)
+{
+    for (int r = 0; r < count; ++r) {
+        E[r]->in_launches.clear();
+        E[r]->sk_launches.clear();
+        E[r]->ld_launches.clear();
+        E[r]->in_max_margin = 16;
+        E[r]->in_src.assign((size_t)3 * n, nullptr);
+    }
+    E[0]->ld_rungs.assign(E, E + count);
+}
+
+// the fan-out is on encoders[0]'s stream: drained (the caller's frames and
+// tables may go, too), the rungs are coded in the order of `encoders`
+static int32_t ld_code(hl_amd_encoder_t* const* E, int count, int n, const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* results)
+{
+    HL_HIP_CHECK(hipStreamSynchronize(E[0]->stream));
+    std::vector<const uint8_t*> y(n), u(n), v(n);
+    for (int r = 0; r < count; ++r) {
+        hl_amd_encoder_t* e = E[r];
+        for (int i = 0; i < n; ++i) {
+            y[i] = e->in_src[3 * (size_t)i];
+            u[i] = e->in_src[3 * (size_t)i + 1];
+            v[i] = e->in_src[3 * (size_t)i + 2];
+        }
+        e->in_nested = true;
+        const int32_t rc = encode_pictures(e, n, y.data(), u.data(), v.data(), results + (size_t)r * n, ctl ? ctl + (size_t)r * n : nullptr);
+        e->in_nested = false;
+        e->in_ok = rc == HL_AMD_SUCCESS;
+        if (rc) {  // the rungs before r have committed; the later ones are untouched
+            if (r + 1 < count) memset(results + (size_t)(r + 1) * n, 0, sizeof(hl_amd_result_t) * (size_t)(count - r - 1) * n);
+            return rc;
+        }
+    }
+    return HL_AMD_SUCCESS;
+}
+
+extern "C" int32_t hl_amd_encode_ladder_frame(hl_amd_encoder_t* const* E, int32_t count, const hl_amd_frame_t* f, const hl_amd_frame_ctl_t* ctl,
+                                              hl_amd_result_t* results)
+{
+    SkParm parm[kLdMaxRungs];
+    int32_t rc = ld_check(E, count, 1, f, ctl, results, true, parm);
+    if (rc) return rc;
+    hl_amd_encoder_t* e0 = E[0];
+    const int sw = parm[0].sw, sh = parm[0].sh, sp = parm[0].sp;
+    uint8_t* mid[3];
+    rc = ld_source(e0, sp, sh, 1, 0, mid);
+    if (rc) return rc;
+    ld_begin(E, count, 1);
+    InArgs A{};
+    if (f->on_device) A.one = in_describe(*f, sw);
+    else {
+        rc = in_stage(e0, *f, sw, sh, &A.one);
+        if (rc) return rc;
+    }
+    LdArgs L{};
+    for (int c = 0; c < 3; ++c) L.one.src[c] = A.one.dst[c] = mid[c];
+    A.coef = in_coef_of(e0->in_matrix, e0->in_range);
+    A.W = sp;
+    A.H = (sh + 15) & ~15;
+    A.dW = sw;
+    A.dH = sh;
+    HL_HIP_CHECK(launch_ingest(A, f->format, 1, e0->stream));
+    e0->in_launches.push_back({A, f->format, 1});
+    L.count = count;
+    for (int r = 0; r < count; ++r) {
+        L.rung[r].parm = parm[r];
+        for (int c = 0; c < 3; ++c) E[r]->in_src[c] = L.rung[r].dst[c] = E[r]->d_in[c];
+    }
+    HL_HIP_CHECK(launch_ladder(L, 1, e0->stream));
+    e0->ld_launches.push_back({L, 1});
+    return ld_code(E, count, 1, ctl, results);
+}
+
+extern "C" int32_t hl_amd_encode_ladder_frames(hl_amd_encoder_t* const* E, int32_t count, int32_t n, const hl_amd_frame_t* f,
+                                               const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* results)
+{
+    SkParm parm[kLdMaxRungs];
+    int32_t rc = ld_check(E, count, n, f, ctl, results, false, parm);
+    if (rc) return rc;
+    hl_amd_encoder_t* e0 = E[0];
+    const int sw = parm[0].sw, sh = parm[0].sh, sp = parm[0].sp;
+    const size_t m = (size_t)n;  // every frame is converted
+    for (int r = 0; r < count; ++r) {  // every rung's planes, as hl_amd_encode_frames grows them
+        hl_amd_encoder_t* e = E[r];
+        const size_t fb = (size_t)e->W * e->H + 2 * (size_t)e->Wc * e->Hc;
+        if (e->inb_cap < fb * m) {
+            (void)hipFree(e->d_inb);
+            e->d_inb = nullptr;
+            e->inb_cap = 0;
+            if (hipMalloc(&e->d_inb, fb * m) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+            e->inb_cap = fb * m;
+        }
+    }
+    if (e0->in_tab_cap < m) {
+        (void)hipFree(e0->d_in_tab);
+        e0->d_in_tab = nullptr;
+        e0->in_tab_cap = 0;
+        if (hipMalloc(&e0->d_in_tab, sizeof(InFrame) * m) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e0->in_tab_cap = m;
+    }
+    uint8_t* mid[3];
+    rc = ld_source(e0, sp, sh, m, 0, mid);
+    if (rc) return rc;
+    if (e0->sk_tab_cap < m) {
+        (void)hipFree(e0->d_sk_tab);
+        e0->d_sk_tab = nullptr;
+        e0->sk_tab_cap = 0;
+        if (hipMalloc(&e0->d_sk_tab, sizeof(SkFrame) * m) != hipSuccess) return HL_AMD_ERROR_OUTOFMEMMORY;
+        e0->sk_tab_cap = m;
+    }
+    ld_begin(E, count, n);
+    // the tables, format by format (one ingest launch per format); frame i's planes are slot j's, for every rung
+    e0->sk_tab.clear();
+    e0->in_tab.clear();
+    size_t first[IN_FORMATS + 1] = {};
+    for (int fmt = 0; fmt < IN_FORMATS; ++fmt) {
+        first[fmt] = e0->in_tab.size();
+        for (int i = 0; i < n; ++i) {
+            if (f[i].format != fmt) continue;
+            const size_t j = e0->in_tab.size();
+            InFrame F = in_describe(f[i], sw);
+            SkFrame S{};
+            (void)ld_source(e0, sp, sh, m, j, F.dst);  // (grown above)
+            for (int c = 0; c < 3; ++c) S.src[c] = F.dst[c];
+            for (int r = 0; r < count; ++r) {
+                hl_amd_encoder_t* e = E[r];
+                const size_t ny = (size_t)e->W * e->H, nc = (size_t)e->Wc * e->Hc;
+                uint8_t* d = e->d_inb + (ny + 2 * nc) * j;
+                e->in_src[3 * (size_t)i] = d;
+                e->in_src[3 * (size_t)i + 1] = d + ny;
+                e->in_src[3 * (size_t)i + 2] = d + ny + nc;
+            }
+            e0->sk_tab.push_back(S);
+            e0->in_tab.push_back(F);
+        }
+    }
+    first[IN_FORMATS] = e0->in_tab.size();
+    HL_HIP_CHECK(hipMemcpyAsync(e0->d_in_tab, e0->in_tab.data(), sizeof(InFrame) * m, hipMemcpyHostToDevice, e0->stream));
+    for (int fmt = 0; fmt < IN_FORMATS; ++fmt)
+        for (size_t f0 = first[fmt]; f0 < first[fmt + 1]; f0 += 65535) {  // grid z holds the frames
+            InArgs A{};
+            A.tab = e0->d_in_tab + f0;
+            A.coef = in_coef_of(e0->in_matrix, e0->in_range);
+            A.W = sp;
+            A.H = (sh + 15) & ~15;
+            A.dW = sw;
+            A.dH = sh;
+            const int frames = (int)std::min<size_t>(65535, first[fmt + 1] - f0);
+            HL_HIP_CHECK(launch_ingest(A, fmt, frames, e0->stream));
+            e0->in_launches.push_back({A, fmt, frames});
+        }
+    HL_HIP_CHECK(hipMemcpyAsync(e0->d_sk_tab, e0->sk_tab.data(), sizeof(SkFrame) * m, hipMemcpyHostToDevice, e0->stream));
+    for (size_t f0 = 0; f0 < m; f0 += (size_t)ld_max_frames(count)) {  // grid z holds frames x rungs
+        LdArgs L{};
+        L.tab = e0->d_sk_tab + f0;
+        L.count = count;
+        for (int r = 0; r < count; ++r) {
+            hl_amd_encoder_t* e = E[r];
+            const size_t ny = (size_t)e->W * e->H, nc = (size_t)e->Wc * e->Hc;
+            L.rung[r].parm = parm[r];
+            L.rung[r].stride = ny + 2 * nc;
+            L.rung[r].dst[0] = e->d_inb + L.rung[r].stride * f0;
+            L.rung[r].dst[1] = L.rung[r].dst[0] + ny;
+            L.rung[r].dst[2] = L.rung[r].dst[1] + nc;
+        }
+        const int frames = (int)std::min<size_t>((size_t)ld_max_frames(count), m - f0);
+        HL_HIP_CHECK(launch_ladder(L, frames, e0->stream));
+        e0->ld_launches.push_back({L, frames});
+    }
+    return ld_code(E, count, n, ctl, results);
+}
+
+// k_scale_fan alone: `iters` times the fan-out launches of the last ladder call
+// (the same intermediate planes into every rung's planes), timed like hl_amd_bench_scale.
+extern "C" int32_t hl_amd_bench_ladder(hl_amd_encoder_t* e, int32_t iters, float* ms)
+{
+    if (!e || iters <= 0 || !ms) return HL_AMD_ERROR_INVALID_PARAMETER;
+    if (!e->in_ok || e->ld_launches.empty() || e->ld_rungs.size() != (size_t)e->ld_launches[0].A.count) return HL_AMD_ERROR_INVALID_STATE;
+    for (size_t r = 0; r < e->ld_rungs.size(); ++r) {  // every rung's last call is still that ladder call
+        const hl_amd_encoder_t* er = e->ld_rungs[r];
+        if (!er->in_ok || er->in_src.size() < 3 || er->in_src[0] != e->ld_launches[0].A.rung[r].dst[0]) return HL_AMD_ERROR_INVALID_STATE;
+    }
+    hipEvent_t a, b;
+    HL_HIP_CHECK(hipEventCreate(&a));
+    HL_HIP_CHECK(hipEventCreate(&b));
+    for (const auto& L : e->ld_launches) HL_HIP_CHECK(launch_ladder(L.A, L.frames, e->stream));  // warm
+    HL_HIP_CHECK(hipEventRecord(a, e->stream));
+    for (int i = 0; i < iters; ++i)
+        for (const auto& L : e->ld_launches) HL_HIP_CHECK(launch_ladder(L.A, L.frames, e->stream));
     HL_HIP_CHECK(hipEventRecord(b, e->stream));
     HL_HIP_CHECK(hipEventSynchronize(b));
     float t = 0.f;

@@ -866,6 +866,59 @@ int32_t hl_amd_scale_taps(int32_t s, int32_t d, int32_t j, int32_t* first, uint3
  * succeed.  No reference interface (like hl_amd_bench_ingest). */
 int32_t hl_amd_bench_scale(hl_amd_encoder_t* encoder, int32_t iters, float* ms);
 
+/* ---- a rendition ladder from one source ----
+ * No reference interface: the reference has no scaler (see above).  `count`
+ * encoders (1 to 8, distinct, on one device; the "rungs") are fed from the
+ * same frame(s) of one common source size in one call: the frame(s) go ONCE
+ * through the staging and k_ingest at the source size into encoders[0]'s
+ * intermediate buffer, one k_scale_fan launch (hartallo_amd/csrc/hl_ladder.h;
+ * several when frames x count exceed a grid dimension) writes every rung's
+ * coded planes with the area filter above, and the rungs are then coded one
+ * after another in the order of `encoders`.  Every rung is the direct area
+ * filter of the source, never a cascade of another rung.
+ * Contract: the results of rung r are exactly those of hl_amd_encode_frame
+ * (hl_amd_encode_frames) on encoders[r] alone with the same frame(s) and its
+ * own ctl: its own stream bytes, GOP counter and idr_pic_id, rate control,
+ * scene cuts and quality, split into runs and failure contract.  Nothing is
+ * forwarded: hl_amd_get_input(encoders[r], k, ...) returns rung r's scaled,
+ * padded planes for every rung, an identity rung included.
+ * Checked for every encoder, frame and ctl before anything is uploaded,
+ * converted or launched (a refused call leaves every stream as it was):
+ *   - count outside 1..8, a null or repeated encoder, encoders on different
+ *     devices: HL_AMD_ERROR_INVALID_PARAMETER;
+ *   - an encoder with spatial layers: HL_AMD_ERROR_NOT_IMPLEMENTED;
+ *   - hl_amd_get_source_size must return the same (sw, sh) for every encoder
+ *     (an encoder without a source size whose display size is (sw, sh) is an
+ *     identity rung: the same filter with s = d), and every encoder must have
+ *     the same hl_amd_set_colour setting (the conversion happens once), else
+ *     HL_AMD_ERROR_INVALID_PARAMETER;
+ *   - the frames as in the per-encoder calls, at the source size: the 4-byte
+ *     rule of device planes always applies; host frames are taken by the
+ *     single-frame call only;
+ *   - frames queued by the look-ahead on any encoder, and for the single-frame
+ *     call look-ahead on at all: HL_AMD_ERROR_INVALID_STATE;
+ *   - ctl (null, or ctl[r * n + i] for frame i of rung r) as in the
+ *     per-encoder calls, against rung r's size;
+ *   - a broken encoder: HL_AMD_ERROR_INVALID_STATE.
+ * If coding rung r fails after the checks, the rungs before it have committed
+ * and keep their results, r follows its own call's failure contract, the
+ * later rungs are untouched with their results zeroed, and r's error is
+ * returned.  results[r * n + i]: frame i of rung r, valid until the next call
+ * on encoders[r].  Left out: look-ahead ladders, rungs coded concurrently or
+ * in one shared run, rungs with spatial layers, upscaling rungs, per-rung
+ * colour settings. */
+int32_t hl_amd_encode_ladder_frame(hl_amd_encoder_t* const* encoders, int32_t count, const hl_amd_frame_t* frame,
+                                   const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* results);
+int32_t hl_amd_encode_ladder_frames(hl_amd_encoder_t* const* encoders, int32_t count, int32_t n, const hl_amd_frame_t* frames,
+                                    const hl_amd_frame_ctl_t* ctl, hl_amd_result_t* results);
+
+/* Diagnostics: `iters` times the k_scale_fan launch(es) of the last ladder
+ * call, whose first encoder this is (the same intermediate planes into every
+ * rung's planes; no other call on any of its encoders since); *ms = average
+ * ms per repetition.  HL_AMD_ERROR_INVALID_STATE otherwise.  No reference
+ * interface (like hl_amd_bench_scale). */
+int32_t hl_amd_bench_ladder(hl_amd_encoder_t* encoder0, int32_t iters, float* ms);
+
 /* device time (ms) of the enhancement layers of the last access unit (with
  * hl_amd_set_timing on) */
 float hl_amd_svc_layer_ms(hl_amd_encoder_t* encoder);
